@@ -1,8 +1,14 @@
 """Benchmark: train crops/s for clip_vit_b_16 + deep VPT(32) + DMCount at 224x224 on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--crops-per-gpu B] [--dtype fp16|bf16|fp32]
+    python bench.py --full                     (+ the in-step kernel timing pass and the CPU baseline)
+    python bench.py --dump-outputs DIR         (+ the last timed step's outputs as DIR/<name>.npy)
     python bench.py --model clip_resnet50      (BASELINE configs[1]: 448 crops, reduction 8, word prompts,
                                                 DMCount, bf16, 8 crops per GPU; a secondary line)
+
+A plain run sets up, warms up, times the K steps and prints the result line; every other measurement
+(roofline / kernels / sinkhorn, cpu_baseline below) takes steps of its own after the timed ones and runs
+only with --full.
 
 One step = forward (autocast, like the reference train.py:36-40) + DACE/DMCount loss (on-device
 Sinkhorn) + backward + GradScaler/Adam step over the 11.3 M trainable parameters, on synthetic crops
@@ -12,7 +18,9 @@ SyncBatchNorm as trainer.py:147, BASELINE configs[3] (32 crops per GPU, weak sca
 without a launcher starts `torch.distributed.run` itself (before this process touches the GPU).
 Rank 0 prints ONE JSON line:
   value        crops/s over all ranks, K timed steps between barriers + device syncs, max over ranks
-  median_ms    median per-step time (HIP events on the step stream; BASELINE.md "Timing")
+  ms_per_step  the timed region's wall time / K
+  median_ms_per_step  median per-step time (HIP events on the step stream; BASELINE.md "Timing")
+and with --full also:
   roofline     the step's dominant kernel by in-step time (every instrumented launch of a few extra steps
                bracketed by HIP events on its own stream, ebc_probe_*): algorithmic FLOP per launch (2*M*N*K,
                K of a conv weight gradient = the B*H*W interior pixels, not its padded K loop) / its average
@@ -62,10 +70,17 @@ def parse(argv=None):
     ap.add_argument("--dtype", default=None, choices=["fp16", "bf16", "fp32"],
                     help="default fp16 (the reference's AMP) for clip_vit_b_16, bf16 for clip_resnet50 (configs[1])")
     ap.add_argument("--pool", type=int, default=64, help="distinct synthetic batches (cycled beyond that)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the instrumented in-step kernel "
+                         "timing pass (roofline / kernels / sinkhorn; --no-probe drops it) and the CPU baseline "
+                         "(--no-cpu-baseline drops it); --augment: the device-only pass and its CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (and, for the train step, the "
+                         "parameters it left) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-crops", type=int, default=16, help="crops per CPU-baseline step (BASELINE.md: 16)")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-baseline steps after 3 warm-up (BASELINE.md)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the instrumented in-step kernel timing pass")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the instrumented in-step kernel timing pass")
     ap.add_argument("--no-ln-fold", action="store_true",
                     help="A/B: ln_1 / ln_2 as LayerNorm launches instead of folded into the QKV / c_fc products")
     ap.add_argument("--touch", type=int, default=None, choices=[0, 1],
@@ -94,6 +109,10 @@ def parse(argv=None):
     ap.add_argument("--noise-rng", default="device", choices=["device", "reference"],
                     help="--augment: salt-and-pepper uniforms from the device hash or the reference's host rand_like")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.classes_out and (not a.full or a.no_probe):
+        ap.error("--classes-out is written by the in-step kernel timing pass: it needs --full (without --no-probe)")
     rn = a.model == "clip_resnet50"
     if a.crops_per_gpu is None:
         a.crops_per_gpu = 8 if rn else (16 if a.gpus == 1 else 32)
@@ -300,9 +319,37 @@ def setup(args, rank, world, local, device):
         # loss's own [5] term vector (loss, ot, tv, count, ce), no stack launch
         if dist.is_initialized():
             dist.all_reduce(loss_fn.last_terms)
+        return logits, exp, loss
     step.pool = pool
     step.loss_fn = loss_fn
+    step.params = params
     return step
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_ELEMS = 4 << 20           # per array: larger ones are written as a fixed, seeded sample (16 MB of float32)
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: tensor or array} as outdir/<name>.npy in float32; an array of more than DUMP_MAX_ELEMS
+    elements as the DUMP_MAX_ELEMS of its flattened elements at sorted indices drawn once from PCG64(0)."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+def train_outputs(step, last):
+    """What a caller of the train step holds after it: the step's logits, density map and loss, the loss's
+    [5] term vector (loss, ot, tv, count, ce) and the trainable parameters the optimizer step left."""
+    logits, exp, loss = last
+    return {"logits": logits, "density": exp, "loss": loss.reshape(1), "loss_terms": step.loss_fn.last_terms,
+            "params": torch.cat([p.detach().reshape(-1).float() for p in step.params])}
 
 
 # ----------------------------------------------------------------------------- in-step kernel timing
@@ -520,34 +567,44 @@ def run_augment(args, rank, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        aug(imgs, labels, NC)
+        last = aug(imgs, labels, NC)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    plans = [aug.plan_crop(i, H, W, labels[i].clone())[0] for i in range(NI) for _ in range(NC)]
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
-        aug.apply(imgs, plans)
-    e1.record()
-    torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1) / 10
+    if args.dump_outputs and rank == 0:
+        crop_imgs, crop_pts, crop_dens = last
+        dump_outputs(args.dump_outputs, {"images": crop_imgs, "density": crop_dens,
+                                         "points": torch.cat([p.reshape(-1, 2).float().cpu() for p in crop_pts], 0)})
     if rank == 0:
-        cpu_imgs = [x.cpu() for x in imgs[:2]]
-        sample = [p for p in plans if p.image < 2]
-        t1 = time.perf_counter()
-        augment_ref.apply_plans(cpu_imgs, sample, (224, 224))
-        cpu_el = time.perf_counter() - t1
         crops = NI * NC * args.steps
-        print(json.dumps({
+        out = {
             "metric": "train-augment crops/s (RandomResizedCrop+flip+jitter+blur+noise+normalise+dot maps, trainer defaults)",
             "value": round(crops / el, 2), "unit": "crops/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True, "vs_baseline": None, "dtype": "f32",
             "data": "synthetic 1536x2048 images in HBM, 200 points each",
-            "config": {"workload": f"{NI} images x {NC} crops -> 224x224 (SURVEY §8f f2)", "noise_rng": args.noise_rng},
-            "device_ms_per_step": round(dev_ms, 4),
-            "cpu_baseline": {"value": round(len(sample) / cpu_el, 2), "unit": "crops/s", "cores": torch.get_num_threads(),
-                             "kind": "port", "sample": f"{len(sample)} crops of the same plans through oracle/augment_ref.py "
-                                                       f"(torch CPU ops the reference's workers run); {cpu_el:.2f}s"}}), flush=True)
+            "config": {"workload": f"{NI} images x {NC} crops -> 224x224 (SURVEY §8f f2)", "noise_rng": args.noise_rng}}
+    if args.full:
+        plans = [aug.plan_crop(i, H, W, labels[i].clone())[0] for i in range(NI) for _ in range(NC)]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            aug.apply(imgs, plans)
+        e1.record()
+        torch.cuda.synchronize()
+        dev_ms = e0.elapsed_time(e1) / 10
+        if rank == 0:
+            out["device_ms_per_step"] = round(dev_ms, 4)
+            if not args.no_cpu_baseline:
+                cpu_imgs = [x.cpu() for x in imgs[:2]]
+                sample = [p for p in plans if p.image < 2]
+                t1 = time.perf_counter()
+                augment_ref.apply_plans(cpu_imgs, sample, (224, 224))
+                cpu_el = time.perf_counter() - t1
+                out["cpu_baseline"] = {
+                    "value": round(len(sample) / cpu_el, 2), "unit": "crops/s", "cores": torch.get_num_threads(),
+                    "kind": "port", "sample": f"{len(sample)} crops of the same plans through oracle/augment_ref.py "
+                                              f"(torch CPU ops the reference's workers run); {cpu_el:.2f}s"}
+    if rank == 0:
+        print(json.dumps(out), flush=True)
 
 
 def run_eval(args, rank, world, device):
@@ -587,12 +644,15 @@ def run_eval(args, rank, world, device):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"density": out})
     if rank == 0:
         tiles = rows * cols
         print(json.dumps({
             "metric": "eval tiles/s clip_vit_b_16 sliding window 2048x3072 (window 224, stride 224)",
             "value": round(tiles * args.steps / elapsed, 2), "unit": "tiles/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_image": round(elapsed / args.steps * 1e3, 3),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "ms_per_image": round(elapsed / args.steps * 1e3, 3),
             "images_per_s": round(args.steps / elapsed, 3), "higher_is_better": True, "scaling": "strong",
             "roofline": {"bound": "mfma", "flop_per_tile": EVAL_FLOP_PER_TILE,
                          "achieved": round(tiles * args.steps / elapsed * EVAL_FLOP_PER_TILE / 1e12 / world, 2),
@@ -651,7 +711,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         ev[i].record(st)
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     ev[-1].record(st)
     torch.cuda.synchronize()
     if world > 1:
@@ -671,8 +731,12 @@ def main():
     value = crops / elapsed
     ms = elapsed / args.steps * 1e3
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(step, last))
+    del last
+
     kernels, sink = None, None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         first = args.warmup + args.steps
         kernels, dace_steps = probe_steps(step, first, 3, device, trace=not args.no_trace,
                                           classes_out=args.classes_out if rank == 0 else None)
@@ -721,7 +785,7 @@ def main():
                     k["pmc_mfma_busy"], k["pmc_traffic"] = kp["mfma_busy"], kp["traffic"]
             out["kernels"] = kernels[:24]
             out["sinkhorn"] = sink
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if rn:
                 out["cpu_baseline"] = cpu_baseline_resnet(args, 2, 5)
             else:

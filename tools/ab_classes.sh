@@ -8,7 +8,7 @@ O=gpurun_out; mkdir -p $O
 for r in 1 2; do
   for l in "$@"; do
     n=$(echo "$l" | tr './' '_d')
-    timeout -k 10 300 env EBC_LIB_PATH=clip-ebc_amd/lib/$l/libebc_hip.so python -u bench.py $ARGS --no-cpu-baseline \
+    timeout -k 10 300 env EBC_LIB_PATH=clip-ebc_amd/lib/$l/libebc_hip.so python -u bench.py --full $ARGS --no-cpu-baseline \
       > $O/${TAG}_last.log 2>&1 || { echo "FAILED $l"; tail -20 $O/${TAG}_last.log; exit 1; }
     tail -1 $O/${TAG}_last.log > $O/${TAG}_${n}_r$r.json
     python -c "import json; d=json.load(open('$O/${TAG}_${n}_r$r.json')); print('$l r$r', d['value'], d['median_ms_per_step'])"

@@ -3,7 +3,7 @@
 #   tools/gpu_check.sh TAG [tests] [smoke] [bench] [prof] [ddp]
 # tests  the -m gpu suite (per-test timeout, stops at the first failure)
 # smoke  __graft_entry__.smoke()
-# bench  the default bench.py line (in-step roofline probe + CPU baseline) -> gpurun_out/TAG_bench.json
+# bench  the bench.py --full line (in-step roofline probe + CPU baseline) -> TAG_bench.json in the output folder
 # bench32  the same at 32 crops per GPU (the multi-GPU per-rank shape, configs[3]) -> gpurun_out/TAG_bench32.json
 # prof   rocprofv3 --kernel-trace --stats of bench.py, cut to the timed steps (tools/kstats.py --window)
 # ddp    the 2-rank DDP + SyncBN bench path with both ranks on cuda:0 over gloo (a rehearsal, not a scaling number)
@@ -29,11 +29,11 @@ for what in "$@"; do
         || { tail -30 $O/${TAG}_smoke.log; exit 1; }
       tail -1 $O/${TAG}_smoke.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py > $O/${TAG}_bench.log 2>&1 || { tail -30 $O/${TAG}_bench.log; exit 1; }
+      timeout -k 10 600 python -u bench.py --full > $O/${TAG}_bench.log 2>&1 || { tail -30 $O/${TAG}_bench.log; exit 1; }
       tail -1 $O/${TAG}_bench.log > $O/${TAG}_bench.json; cut -c1-400 $O/${TAG}_bench.json ;;
     bench32)
       # the multi-GPU runs' per-rank shape (configs[3]: 32 crops per GPU) on this one GPU
-      timeout -k 10 600 python -u bench.py --crops-per-gpu 32 --steps 30 --warmup 8 --no-cpu-baseline > $O/${TAG}_bench32.log 2>&1 \
+      timeout -k 10 600 python -u bench.py --full --crops-per-gpu 32 --steps 30 --warmup 8 --no-cpu-baseline > $O/${TAG}_bench32.log 2>&1 \
         || { tail -30 $O/${TAG}_bench32.log; exit 1; }
       tail -1 $O/${TAG}_bench32.log > $O/${TAG}_bench32.json; cut -c1-400 $O/${TAG}_bench32.json ;;
     prof)
@@ -53,7 +53,7 @@ for what in "$@"; do
         > $O/${TAG}_tsel.log 2>&1 || { tail -60 $O/${TAG}_tsel.log; exit 1; }
       tail -1 $O/${TAG}_tsel.log ;;
     rbench)
-      timeout -k 10 600 python -u bench.py --model clip_resnet50 --steps 20 --warmup 5 > $O/${TAG}_rbench.log 2>&1 \
+      timeout -k 10 600 python -u bench.py --full --model clip_resnet50 --steps 20 --warmup 5 > $O/${TAG}_rbench.log 2>&1 \
         || { tail -30 $O/${TAG}_rbench.log; exit 1; }
       tail -1 $O/${TAG}_rbench.log > $O/${TAG}_rbench.json; cut -c1-600 $O/${TAG}_rbench.json ;;
     rprof)
@@ -69,7 +69,7 @@ for what in "$@"; do
     pstep)
       # the bench command itself under rocprofv3: a kernel-trace pass and two --pmc passes (each its own run, its own
       # limit), cut to the timed steps and mapped to bench.py's kernel classes (tools/pmc_step.py)
-      B="$R/bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-trace --classes-out $O/${TAG}_classes.json"
+      B="$R/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-trace --classes-out $O/${TAG}_classes.json"
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ptrace -o run -- \
         python3 $B > $O/${TAG}_ptrace.log 2>&1) || { tail -30 $O/${TAG}_ptrace.log; exit 1; }
       db=$(find $O/${TAG}_ptrace -name "*.db" | head -1)
