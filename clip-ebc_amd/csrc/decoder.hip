@@ -826,7 +826,11 @@ __global__ __launch_bounds__(256) void transpose3_kernel(const T* __restrict__ x
 
 // dfeat = bilinear^T (g), g = conv1's input gradient + the residual branch's (already summed by the
 // dgrad GEMM epilogue): input cell i collects output rows/columns UP*i - UP/2 .. +2*UP-1 (zero weight
-// where a tap misses i); all loads issued without data-dependent branches
+// where a tap misses i); all loads issued without data-dependent branches.
+// UP = 4 (ViT-B/32 at reduction 8, models/clip/model.py:195-196): output o reads src = (o - 1.5) / 4, so cell i is a
+// tap of outputs 4i-2 .. 4i+5 -- the same 2*UP candidates per axis, 8 x 8 of them, with weights that are multiples
+// of 1/8 per axis; at a border the clamped outputs (src < 0, or i0 = h-1 with both taps on the edge cell) put both
+// tap weights on the edge cell, and the candidates beyond the image take weight 0 on a clamped (in-bounds) address.
 template <class T, int UP>
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T* __restrict__ g, float* __restrict__ dfeat, int B,
                                                            int h, int w, int H, int W, int C)
@@ -1199,11 +1203,15 @@ extern "C" int ebc_dec_upsample_bwd(int dtype, const void* g, float* dfeat, int 
                                     ebc_stream_t stream)
 {
     if (!g || !dfeat || C % 4) return EBC_E_ARG;
-    if (up != 1 && up != 2) return EBC_E_UNSUPPORTED;
+    if (up != 1 && up != 2 && up != 4) return EBC_E_UNSUPPORTED;
     if (B <= 0 || h <= 0 || w <= 0 || (long)w * C >= (1L << 31) || (long)B * h >= 65536) return EBC_E_ARG;
     const dim3 grid((unsigned)((w * (C / 4) + 255) / 256), (unsigned)(B * h));
     const hipStream_t st = (hipStream_t)stream;
-    if (up == 2) {
+    if (up == 4) {
+        if ((long)B * h * 4 * w * 4 * C >= (1L << 40)) return EBC_E_ARG;
+        EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((upsample_bwd_kernel<T, 4>), grid, dim3(256), 0, st,
+                                                   (const T*)g, dfeat, B, h, w, 4 * h, 4 * w, C));
+    } else if (up == 2) {
         EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((upsample_bwd_kernel<T, 2>), grid, dim3(256), 0, st,
                                                    (const T*)g, dfeat, B, h, w, 2 * h, 2 * w, C));
     } else {

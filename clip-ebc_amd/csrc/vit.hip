@@ -1,4 +1,4 @@
-// Host-side orchestration of the CLIP ViT-B/16 + deep-VPT encoder (forward, and dX-only backward
+// Host-side orchestration of the CLIP ViT-B/16 and ViT-B/32 + deep-VPT encoder (forward, and dX-only backward
 // with the per-layer VPT gradients), plus the C-ABI wrappers of the individual kernels.
 //
 // Reference: CLIP_EBC._forward_vpt   models/clip/model.py:142-189
@@ -59,7 +59,8 @@ struct Layout {
     size_t bytes;
 };
 
-Layout carve(void* ws, int B, int L, int G, int layers, int dtype, int training)
+// KP = 3 * patch^2, the patch GEMM's K (768 at patch 16 -- the same bytes as before the patch size was a parameter)
+Layout carve(void* ws, int B, int L, int G, int KP, int layers, int dtype, int training)
 {
     const size_t M = (size_t)B * L;
     const size_t es = dtype == EBC_F32 ? 4 : 2;
@@ -87,7 +88,7 @@ Layout carve(void* ws, int B, int L, int G, int layers, int dtype, int training)
     }
     lay.H = c.take<void>(M * WIDTH * es);
     lay.G = c.take<void>(M * MLP * es);
-    lay.patch_t = c.take<void>((size_t)B * G * WIDTH * es);
+    lay.patch_t = c.take<void>((size_t)B * G * KP * es);
     lay.patch_f = c.take<float>((size_t)B * G * WIDTH * 4);
     lay.mpost = c.take<float>((size_t)B * G * 4);
     lay.rpost = c.take<float>((size_t)B * G * 4);
@@ -122,7 +123,7 @@ Layout carve(void* ws, int B, int L, int G, int layers, int dtype, int training)
         lay.rpart = nullptr;
     }
     // the largest split-K workspace any of the encoder GEMMs asks for
-    size_t g = ebc::gemm_workspace_bytes(dtype, B * G, WIDTH, WIDTH);          // patch embedding
+    size_t g = ebc::gemm_workspace_bytes(dtype, B * G, WIDTH, KP);             // patch embedding
     const int Mi = (int)M;
     const int shapes[][2] = {{QKVW, WIDTH}, {WIDTH, WIDTH}, {MLP, WIDTH}, {WIDTH, MLP}, {WIDTH, QKVW}};
     for (const auto& sh : shapes) g = std::max(g, ebc::gemm_workspace_bytes(dtype, Mi, sh[0], sh[1]));
@@ -132,27 +133,40 @@ Layout carve(void* ws, int B, int L, int G, int layers, int dtype, int training)
     return lay;
 }
 
+// ViT-B/16 and ViT-B/32: the patch size only sets the token grid and the patch GEMM's K
+inline bool patch_ok(int patch) { return patch == 16 || patch == 32; }
+
 bool check_weights(const EbcVitWeights* w) {
-    return w && w->layers > 0 && w->layer && w->width == WIDTH && w->heads == HEADS && w->patch == 16 && w->num_vpt >= 0;
+    return w && w->layers > 0 && w->layer && w->width == WIDTH && w->heads == HEADS && patch_ok(w->patch) && w->num_vpt >= 0;
 }
 
 }  // namespace
 
+extern "C" size_t ebc_vit_workspace_bytes_p(int B, int H, int W, int patch, int layers, int num_vpt, int dtype, int training)
+{
+    if (!patch_ok(patch) || B <= 0 || H < patch || W < patch || layers <= 0 || num_vpt < 0) return 0;
+    const int G = (H / patch) * (W / patch), L = 1 + num_vpt + G;
+    return carve(nullptr, B, L, G, 3 * patch * patch, layers, dtype, training).bytes;
+}
+
 extern "C" size_t ebc_vit_workspace_bytes(int B, int H, int W, int layers, int num_vpt, int dtype, int training)
 {
     const int G = (H / 16) * (W / 16), L = 1 + num_vpt + G;
-    return carve(nullptr, B, L, G, layers, dtype, training).bytes;
+    return carve(nullptr, B, L, G, 3 * 16 * 16, layers, dtype, training).bytes;
 }
 
 extern "C" int ebc_vit_forward(const EbcVitWeights* w, const float* image, int B, int H, int W,
                                const float* const* vpt, long vpt_bstride, int dtype, int training,
                                void* ws, size_t ws_bytes, float* feat, ebc_stream_t stream)
 {
-    if (!check_weights(w) || !image || !ws || !feat || B <= 0 || H % 16 || W % 16) return EBC_E_ARG;
+    if (!check_weights(w) || !image || !ws || !feat || B <= 0 || H < w->patch || W < w->patch || H % w->patch ||
+        W % w->patch)
+        return EBC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int NV = w->num_vpt, G = (H / 16) * (W / 16), L = 1 + NV + G, layers = w->layers;
+    const int P = w->patch, KP = 3 * P * P;
+    const int NV = w->num_vpt, G = (H / P) * (W / P), L = 1 + NV + G, layers = w->layers;
     if (L > 16384) return EBC_E_UNSUPPORTED;                 // attention.hip L_MAX
-    Layout lay = carve(ws, B, L, G, layers, dtype, training);
+    Layout lay = carve(ws, B, L, G, KP, layers, dtype, training);
     if (lay.bytes > ws_bytes) return EBC_E_ARG;
     if (NV > 0 && (!vpt || !vpt[0])) return EBC_E_ARG;
     if (lay.gws && hipMemsetAsync(lay.gws, 0, std::min<size_t>(lay.gws_bytes, 16 * 1024), st) != hipSuccess)
@@ -162,9 +176,9 @@ extern "C" int ebc_vit_forward(const EbcVitWeights* w, const float* image, int B
         return ebc::gemm_nt(dtype, epi, out_f32, A, Bm, C, bias, resid, aux, m, n, k, st, lay.gws, lay.gws_bytes);
     };
 
-    // patch embedding: im2col + GEMM with conv1 weight [768, 3*16*16] (image_encoder.py:141)
-    EBC_TRY(ebc::im2col(dtype, image, lay.patch_t, B, H, W, 16, st));
-    EBC_TRY(gemm(EBC_EPI_STORE, 1, lay.patch_t, w->w_patch, lay.patch_f, nullptr, nullptr, nullptr, B * G, WIDTH, WIDTH));
+    // patch embedding: im2col + GEMM with conv1 weight [768, 3*patch*patch] (image_encoder.py:141)
+    EBC_TRY(ebc::im2col(dtype, image, lay.patch_t, B, H, W, P, st));
+    EBC_TRY(gemm(EBC_EPI_STORE, 1, lay.patch_t, w->w_patch, lay.patch_f, nullptr, nullptr, nullptr, B * G, WIDTH, KP));
     // CLS + pos + ln_pre, VPT_0 rows (model.py:150-168)
     EBC_TRY(ebc::embed_tokens(lay.patch_f, w->cls, w->pos, w->ln_pre_g, w->ln_pre_b, NV ? vpt[0] : nullptr,
                               vpt_bstride, lay.X[0], B, L, G, NV, WIDTH, st));
@@ -274,11 +288,13 @@ extern "C" int ebc_vit_forward(const EbcVitWeights* w, const float* image, int B
 extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int dtype, void* ws, size_t ws_bytes,
                                 const float* dfeat, float* const* dvpt, long vpt_bstride, int flags, ebc_stream_t stream)
 {
-    if (!check_weights(w) || !ws || !dfeat) return EBC_E_ARG;
+    if (!check_weights(w) || !ws || !dfeat || B <= 0 || H < w->patch || W < w->patch || H % w->patch || W % w->patch)
+        return EBC_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int NV = w->num_vpt, G = (H / 16) * (W / 16), L = 1 + NV + G, layers = w->layers;
+    const int P = w->patch;
+    const int NV = w->num_vpt, G = (H / P) * (W / P), L = 1 + NV + G, layers = w->layers;
     const int M = B * L;
-    Layout lay = carve(ws, B, L, G, layers, dtype, 1);
+    Layout lay = carve(ws, B, L, G, 3 * P * P, layers, dtype, 1);
     if (lay.bytes > ws_bytes) return EBC_E_ARG;
     const int per_batch = vpt_bstride != 0;
 
@@ -416,6 +432,11 @@ extern "C" int ebc_head_bwd(int dtype_z, int dtype_dz, const void* Z, const floa
 {
     return ebc::head_bwd(dtype_z, dtype_dz, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dZ, dbias, dscale, P, HW,
                          NB, embed, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int ebc_im2col(int dtype, const float* x, void* out, int B, int H, int W, int patch, ebc_stream_t stream)
+{
+    if (!x || !out || B <= 0 || patch <= 0 || H < patch || W < patch) return EBC_E_ARG;
+    return ebc::im2col(dtype, x, out, B, H, W, patch, (hipStream_t)stream);
 }
 extern "C" int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream)
 {

@@ -1,4 +1,4 @@
-"""Drop-in CLIP-EBC model (ViT-B/16 + deep VPT) whose hot path runs in libebc_hip.so.
+"""Drop-in CLIP-EBC model (ViT-B/16 or ViT-B/32 + deep VPT) whose hot path runs in libebc_hip.so.
 
 Reference surface kept:
   * `get_model(backbone, input_size, reduction, bins, anchor_points, **kw)`  (models/__init__.py:10-44)
@@ -32,6 +32,15 @@ from . import synthetic
 from .text import CLIPTextEncoder, format_count, prompt_tokens
 
 WIDTH, HEADS, PATCH, EMBED = 768, 12, 16, 512
+
+# Per-backbone geometry of the CLIP ViT towers on the HIP path (models/clip/model.py:21-22: reduction = patch, channels
+# 768, embed 512).  B/16 and B/32 share every transformer dimension (width 768, 12 heads, MLP 3072; text tower
+# 512 / 8 / 12); the patch size sets the token grid, the patch GEMM's K = 3 * patch^2 and the encoder's reduction.
+# `reductions`: the output reductions served (bilinear adapt x patch / reduction, models/clip/model.py:195-196).
+VIT_GEOMETRY: Dict[str, Dict[str, Any]] = {
+    "vit_b_16": dict(patch=16, reductions=(16, 8)),          # x1 / x2
+    "vit_b_32": dict(patch=32, reductions=(32, 16, 8)),      # x1 / x2 / x4
+}
 
 
 # ----------------------------------------------------------------------------- parameter containers
@@ -168,7 +177,8 @@ class _EncoderCache:
                     setattr(L, f"s_{pre}_ln", _p(cvt(wf.double().sum(1), torch.float32)))
                     setattr(L, f"b_{pre}_ln", _p(cvt(bias.detach().to(device, torch.float64)
                                                      + w64 @ ln.bias.detach().to(device, torch.float64), torch.float32)))
-        self.w_patch = cvt(enc.conv1.weight.reshape(WIDTH, -1))
+        self.patch = int(enc.patch_size[0])
+        self.w_patch = cvt(enc.conv1.weight.reshape(WIDTH, -1))                    # [768, 3 * patch^2]
         self.cls = cvt(enc.class_embedding, torch.float32)
         self.ln = [cvt(t, torch.float32) for t in (enc.ln_pre.weight, enc.ln_pre.bias, enc.ln_post.weight, enc.ln_post.bias)]
         self.enc, self.num_vpt, self.layers = enc, num_vpt, layers
@@ -181,7 +191,7 @@ class _EncoderCache:
             with torch.no_grad():
                 pos = self.enc._interpolate_pos_embed(gh, gw).detach().to(self.device, torch.float32).contiguous()
             w = EbcVitWeights()
-            w.layers, w.width, w.heads, w.patch, w.num_vpt = self.layers, WIDTH, HEADS, PATCH, self.num_vpt
+            w.layers, w.width, w.heads, w.patch, w.num_vpt = self.layers, WIDTH, HEADS, self.patch, self.num_vpt
             w.w_patch, w.cls, w.pos = _p(self.w_patch), _p(self.cls), _p(pos)
             w.ln_pre_g, w.ln_pre_b, w.ln_post_g, w.ln_post_b = (_p(t) for t in self.ln)
             w.layer = ctypes.cast(self.layer_arr, ctypes.POINTER(EbcVitLayer))
@@ -190,7 +200,7 @@ class _EncoderCache:
 
 
 class _VitFn(torch.autograd.Function):
-    """ebc_vit_forward / ebc_vit_backward: image -> ln_post(patch tokens) [B, G, 768] f32."""
+    """ebc_vit_forward / ebc_vit_backward: image -> ln_post(patch tokens) [B, G, 768] f32 (G = (H/patch)(W/patch))."""
 
     @staticmethod
     def forward(ctx, cache, image, vpt_bstride, training, *vpts):
@@ -201,11 +211,11 @@ class _VitFn(torch.autograd.Function):
     def _forward(ctx, cache, image, vpt_bstride, training, *vpts):
         L = _lib.lib()
         B, _, H, W = image.shape
-        gh, gw = H // PATCH, W // PATCH
+        gh, gw = H // cache.patch, W // cache.patch
         dt = _lib.dtype_code(cache.dtype)
         dev = image.device
         image = image.detach().float().contiguous()
-        nbytes = L.ebc_vit_workspace_bytes(B, H, W, cache.layers, cache.num_vpt, dt, int(training))
+        nbytes = L.ebc_vit_workspace_bytes_p(B, H, W, cache.patch, cache.layers, cache.num_vpt, dt, int(training))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         feat = torch.empty(B, gh * gw, WIDTH, device=dev, dtype=torch.float32)
         vp = [v.detach().float().contiguous() for v in vpts]
@@ -231,7 +241,7 @@ class _VitFn(torch.autograd.Function):
         B, H, W = ctx.shape
         dvpt = [torch.empty(s, device=dfeat.device, dtype=torch.float32) for s in ctx.vpt_shapes]
         arr = (_VP * cache.layers)(*([_p(v) for v in dvpt] + [None] * (cache.layers - len(dvpt))))
-        w = cache.weights(H // PATCH, W // PATCH)
+        w = cache.weights(H // cache.patch, W // cache.patch)
         rc = L.ebc_vit_backward(ctypes.byref(w), B, H, W, _lib.dtype_code(cache.dtype), _lib.ptr(ctx.ws), ctx.ws.numel(),
                                 _lib.ptr(dfeat.float().contiguous()), arr, ctx.bstride, cache.bwd_flags, _lib.stream(dfeat))
         _lib.check(rc, "ebc_vit_backward")
@@ -567,11 +577,11 @@ class _DecoderFn(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------- model
 resnet_backbones = ["resnet50", "resnet101", "resnet50x4", "resnet50x16", "resnet50x64"]
-vit_backbones = ["vit_b_16"]
+vit_backbones = ["vit_b_16", "vit_b_32"]
 
 
 class CLIP_EBC(nn.Module):
-    """models/clip/model.py:30-217 for the vit_b_16 (deep VPT, frozen encoder) and resnet50 (trainable
+    """models/clip/model.py:30-217 for the vit_b_16 / vit_b_32 (deep VPT, frozen encoder) and resnet50 (trainable
     ModifiedResNet, Bottleneck decoder; ebc_amd/resnet.py) backbones."""
 
     def __init__(self, backbone: str, bins: List[Tuple[float, float]], anchor_points: List[float],
@@ -581,8 +591,13 @@ class CLIP_EBC(nn.Module):
                  text_layers: int = 12, text_features: Optional[Tensor] = None, weights_seed: Optional[int] = None,
                  **kwargs: Any) -> None:
         super().__init__()
+        if backbone in ("vit_l_14", "vit_l_14_336px"):
+            raise NotImplementedError(f"backbone {backbone!r}: the HIP encoder is built for width 768 / 12 heads and patch "
+                                      "16 or 32; ViT-L/14 needs width 1024 (16 heads, MLP 4096) in the LayerNorm and "
+                                      "LN-fold GEMM epilogues, patch 14 (K = 588 patch rows) and the x1.75 bilinear adapt")
         if backbone not in vit_backbones + ["resnet50"]:
-            raise NotImplementedError(f"backbone {backbone!r}: vit_b_16 and resnet50 are on the MI355X path (SURVEY.md §8)")
+            raise NotImplementedError(f"backbone {backbone!r}: vit_b_16, vit_b_32 and resnet50 are on the MI355X path "
+                                      "(SURVEY.md §8)")
         self.backbone = backbone
         if backbone == "resnet50":
             from .resnet import Bottleneck, ModifiedResNet
@@ -603,22 +618,25 @@ class CLIP_EBC(nn.Module):
             assert num_vpt is not None, "Expected num_vpt to be an integer, got None."
             assert deep_vpt is not None, "Expected deep_vpt to be a boolean, got None."
             assert vpt_drop is not None, "Expected vpt_drop to be a float, got None."
-            self.image_encoder = VisionTransformer(input_size, PATCH, EMBED, WIDTH, vit_layers, HEADS)
+            geo = VIT_GEOMETRY[backbone]
+            patch = geo["patch"]
+            self.image_encoder = VisionTransformer(input_size, patch, EMBED, WIDTH, vit_layers, HEADS)
             self.image_encoder_depth = vit_layers
             for p in self.image_encoder.parameters():
                 p.requires_grad = False
             self.num_vpt, self.deep_vpt, self.vpt_drop = num_vpt, deep_vpt, vpt_drop
-            _check_tokens(input_size, input_size, num_vpt)
-            val = math.sqrt(6.0 / float(3 * PATCH + WIDTH))
+            _check_tokens(input_size, input_size, num_vpt, patch, backbone)
+            val = math.sqrt(6.0 / float(3 * patch + WIDTH))                  # models/clip/model.py:70-71
             for idx in range(vit_layers if deep_vpt else 1):
                 setattr(self, f"vpt_{idx}", nn.Parameter(torch.empty(num_vpt, WIDTH).uniform_(-val, val)))
-            self.encoder_reduction = PATCH
+            self.encoder_reduction = patch
             self.reduction = self.encoder_reduction if reduction is None else reduction
             decoder_cfg = decoder_cfg or [WIDTH]
             if list(decoder_cfg) != [WIDTH]:
-                raise NotImplementedError("vit_b_16 decoder is BasicBlock [768] (models/clip/model.py:250-251)")
-            if reduction is not None and (PATCH % reduction or PATCH // reduction not in (1, 2)):
-                raise NotImplementedError("reduction must be 16 or 8 for vit_b_16 (x1 / x2 bilinear adapt)")
+                raise NotImplementedError(f"{backbone} decoder is BasicBlock [768] (models/clip/model.py:250-253)")
+            if reduction is not None and reduction not in geo["reductions"]:
+                ok = " / ".join(f"{r} (x{patch // r})" for r in geo["reductions"])
+                raise NotImplementedError(f"reduction must be one of {ok} for {backbone} (bilinear adapt)")
             self.image_decoder = nn.Sequential(BasicBlock(WIDTH, WIDTH))
             embed = EMBED
         self.channels, self.clip_embed_dim = decoder_cfg[-1], embed
@@ -649,7 +667,8 @@ class CLIP_EBC(nn.Module):
         if self.backbone == "resnet50":
             sd = synthetic.resnet50_full_state(seed, text_layers=text_layers)
         else:
-            sd = synthetic.full_state(seed, layers=vit_layers, text_layers=text_layers, input_size=input_size)
+            sd = synthetic.full_state(seed, layers=vit_layers, text_layers=text_layers, input_size=input_size,
+                                      patch=self.encoder_reduction)
         own = self.state_dict()
         sd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items() if k in own}
         self.load_state_dict(sd, strict=False)
@@ -697,17 +716,17 @@ class CLIP_EBC(nn.Module):
         return vpts, 0
 
     def _forward_vpt_nhwc(self, x: Tensor) -> Tensor:
-        """[B,3,H,W] -> ln_post patch tokens [B,H/16,W/16,768] f32 (NHWC), models/clip/model.py:142-189."""
+        """[B,3,H,W] -> ln_post patch tokens [B,H/patch,W/patch,768] f32 (NHWC), models/clip/model.py:142-189."""
         B, _, H, W = x.shape
         cache = self._encoder_cache(self._compute_dtype(x), x.device)
         vpts, bstride = self._prepare_vpts(B)
         training = torch.is_grad_enabled() and any(v.requires_grad for v in vpts)
         with torch.autocast("cuda", enabled=False):
             feat = _VitFn.apply(cache, x, bstride, training, *vpts)
-        return feat.view(B, H // PATCH, W // PATCH, WIDTH)
+        return feat.view(B, H // cache.patch, W // cache.patch, WIDTH)
 
     def _forward_vpt(self, x: Tensor) -> Tensor:
-        """[B,3,H,W] -> [B,768,H/16,W/16] (channels_last memory), models/clip/model.py:142-189."""
+        """[B,3,H,W] -> [B,768,H/patch,W/patch] (channels_last memory), models/clip/model.py:142-189."""
         return self._forward_vpt_nhwc(x).permute(0, 3, 1, 2)
 
     def _forward_resnet(self, x: Tensor, cdt: torch.dtype) -> Union[Tensor, Tuple[Tensor, Tensor]]:
@@ -733,9 +752,9 @@ class CLIP_EBC(nn.Module):
         cdt = self._compute_dtype(x)
         if self.backbone == "resnet50":
             return self._forward_resnet(x, cdt)
-        _check_tokens(x.shape[-2], x.shape[-1], self.num_vpt)
+        _check_tokens(x.shape[-2], x.shape[-1], self.num_vpt, self.encoder_reduction, self.backbone)
         feat = self._forward_vpt_nhwc(x)
-        up = self.encoder_reduction // self.reduction                      # model.py:195-196 (x2 for reduction 8)
+        up = self.encoder_reduction // self.reduction                      # model.py:195-196 (B/16: x2, B/32: x4 at 8)
         blk = self.image_decoder[0]
         with torch.autocast("cuda", enabled=False):
             y = _DecoderFn.apply(feat, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight,
@@ -748,7 +767,7 @@ class CLIP_EBC(nn.Module):
 def _clip_ebc(backbone: str, bins, anchor_points, reduction=None, freeze_text_encoder=True, prompt_type="number",
               input_size=None, num_vpt=None, deep_vpt=None, vpt_drop=None, decoder_block=None, decoder_cfg=None,
               **kw) -> CLIP_EBC:
-    """models/clip/model.py:220-270 (vit_b_16: BasicBlock decoder [768]; resnet50: Bottleneck decoder [2048])."""
+    """models/clip/model.py:220-270 (vit_b_16 / vit_b_32: BasicBlock decoder [768]; resnet50: Bottleneck decoder [2048])."""
     return CLIP_EBC(backbone, bins, anchor_points, reduction=reduction, freeze_text_encoder=freeze_text_encoder,
                     prompt_type=prompt_type, input_size=input_size, num_vpt=num_vpt, deep_vpt=deep_vpt,
                     vpt_drop=vpt_drop, decoder_cfg=decoder_cfg, **kw)
@@ -757,18 +776,18 @@ def _clip_ebc(backbone: str, bins, anchor_points, reduction=None, freeze_text_en
 MAX_TOKENS = 16384    # attention.hip L_MAX (sequences past 256 tokens stream K / V through LDS in chunks)
 
 
-def _check_tokens(h: int, w: int, num_vpt: int) -> None:
-    """The ViT sequence (CLS + prompts + (h/16)(w/16) patches) must fit the attention kernels' bound."""
-    tokens = 1 + num_vpt + (h // PATCH) * (w // PATCH)
+def _check_tokens(h: int, w: int, num_vpt: int, patch: int = PATCH, backbone: str = "vit_b_16") -> None:
+    """The ViT sequence (CLS + prompts + (h/patch)(w/patch) patches) must fit the attention kernels' bound."""
+    tokens = 1 + num_vpt + (h // patch) * (w // patch)
     if tokens > MAX_TOKENS:
         raise NotImplementedError(
-            f"clip_vit_b_16 on {h}x{w} inputs with {num_vpt} prompts is a sequence of {tokens} tokens; the HIP attention "
+            f"clip_{backbone} on {h}x{w} inputs with {num_vpt} prompts is a sequence of {tokens} tokens; the HIP attention "
             f"kernels take up to {MAX_TOKENS} tokens")
 
 
 def get_model(backbone: str, input_size: int, reduction: int, bins: Optional[List[Tuple[float, float]]] = None,
               anchor_points: Optional[List[float]] = None, **kwargs: Any) -> nn.Module:
-    """models/__init__.py:10-44.  clip_vit_b_16 and clip_resnet50 are on the MI355X path; vgg19_ae (configs[0]) is
+    """models/__init__.py:10-44.  clip_vit_b_16, clip_vit_b_32 and clip_resnet50 are on the MI355X path; vgg19_ae (configs[0]) is
     the reference's DM-Count VGG-19 encoder-decoder (ebc_amd/vgg.py)."""
     backbone = backbone.lower()
     if "clip" not in backbone:

@@ -1,4 +1,4 @@
-"""Deterministic synthetic weights and crops for CLIP-EBC (ViT-B/16 + deep VPT; CLIP ResNet-50, config 2).
+"""Deterministic synthetic weights and crops for CLIP-EBC (ViT-B/16 and ViT-B/32 + deep VPT; CLIP ResNet-50, config 2).
 
 There are no CLIP checkpoints offline (the reference downloads them on import,
 `models/clip/_clip/__init__.py:31-36`), so parity and benchmarking run on weights
@@ -23,9 +23,9 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-WIDTH = 768          # ViT-B/16 width
+WIDTH = 768          # ViT-B/16 and ViT-B/32 width
 HEADS = 12
-PATCH = 16
+PATCH = 16           # ViT-B/16; ViT-B/32 passes patch=32
 EMBED = 512          # CLIP joint embedding
 TEXT_WIDTH = 512
 TEXT_HEADS = 8
@@ -63,12 +63,14 @@ def _block(sd, seed, prefix, width):
     sd[prefix + "mlp.c_proj.bias"] = _normal(seed, prefix + "mlp.c_proj.bias", (width,), 0.02)
 
 
-def vit_state(seed: int = 0, layers: int = 12, input_size: int = 224) -> Dict[str, np.ndarray]:
-    """Frozen CLIP ViT-B/16 visual tower (`image_encoder.py:118-161`), features_only."""
-    g = input_size // PATCH
+def vit_state(seed: int = 0, layers: int = 12, input_size: int = 224, patch: int = PATCH) -> Dict[str, np.ndarray]:
+    """Frozen CLIP ViT-B/16 (patch 16) or ViT-B/32 (patch 32) visual tower (`image_encoder.py:118-161`),
+    features_only.  The patch size changes the shapes of conv1 and the positional embedding only; every tensor is
+    keyed by its name, so patch 16 gives the same arrays as before the argument existed."""
+    g = input_size // patch
     sd: Dict[str, np.ndarray] = {}
     p = "image_encoder."
-    sd[p + "conv1.weight"] = _normal(seed, p + "conv1.weight", (WIDTH, 3, PATCH, PATCH), 1.0 / math.sqrt(3 * PATCH * PATCH))
+    sd[p + "conv1.weight"] = _normal(seed, p + "conv1.weight", (WIDTH, 3, patch, patch), 1.0 / math.sqrt(3 * patch * patch))
     sd[p + "class_embedding"] = _normal(seed, p + "class_embedding", (WIDTH,), WIDTH ** -0.5)
     sd[p + "positional_embedding"] = _normal(seed, p + "positional_embedding", (g * g + 1, WIDTH), WIDTH ** -0.5)
     for ln in ("ln_pre", "ln_post"):
@@ -123,15 +125,15 @@ def text_state(seed: int = 0, layers: int = 12, embed: int = EMBED) -> Dict[str,
     return sd
 
 
-def trainable_state(seed: int = 0, layers: int = 12, deep_vpt: bool = True) -> Dict[str, np.ndarray]:
+def trainable_state(seed: int = 0, layers: int = 12, deep_vpt: bool = True, patch: int = PATCH) -> Dict[str, np.ndarray]:
     """VPT tokens, BasicBlock decoder, projection, logit_scale.
 
-    Init laws follow the reference: VPT U(+-sqrt(6/(3*16+768))) (`models/clip/model.py:70-75`),
+    Init laws follow the reference: VPT U(+-sqrt(6/(3*patch+768))) (`models/clip/model.py:70-75`),
     conv kaiming_normal(fan_out, relu) and BN (1, 0) (`models/utils.py:366-379`),
     logit_scale = ln(1/0.07) (`models/clip/model.py:117`).
     """
     sd: Dict[str, np.ndarray] = {}
-    val = math.sqrt(6.0 / float(3 * PATCH + WIDTH))
+    val = math.sqrt(6.0 / float(3 * patch + WIDTH))
     for i in range(layers if deep_vpt else 1):
         sd[f"vpt_{i}"] = _uniform(seed, f"vpt_{i}", (NUM_VPT, WIDTH), -val, val)
     d = "image_decoder.0."
@@ -150,9 +152,9 @@ def trainable_state(seed: int = 0, layers: int = 12, deep_vpt: bool = True) -> D
 
 
 def full_state(seed: int = 0, layers: int = 12, text_layers: int = 12, input_size: int = 224,
-               include_text: bool = True) -> Dict[str, np.ndarray]:
-    sd = vit_state(seed, layers, input_size)
-    sd.update(trainable_state(seed, layers))
+               include_text: bool = True, patch: int = PATCH) -> Dict[str, np.ndarray]:
+    sd = vit_state(seed, layers, input_size, patch)
+    sd.update(trainable_state(seed, layers, patch=patch))
     if include_text:
         sd.update(text_state(seed, text_layers))
     return sd
@@ -245,6 +247,14 @@ def synthetic_crops(batch: int, size: int = 224, seed: int = 1000, max_points: i
     for b, p in enumerate(points):
         density[b, 0] = point_map(p, size, size)
     return img.astype(np.float32), points, density
+
+
+def synthetic_images(batch: int, height: int, width: int, seed: int = 1000) -> np.ndarray:
+    """Normalised images [B,3,H,W] f32 of any (also non-square) size, pixels as in `synthetic_crops`."""
+    img = crop_rng(seed).random((batch, 3, height, width), dtype=np.float32)
+    mean = np.asarray(IMAGENET_MEAN, np.float32).reshape(1, 3, 1, 1)
+    std = np.asarray(IMAGENET_STD, np.float32).reshape(1, 3, 1, 1)
+    return ((img - mean) / std).astype(np.float32)
 
 
 def point_map(points: np.ndarray, height: int, width: int) -> np.ndarray:

@@ -137,7 +137,7 @@ int ebc_gemm_wgrad(int dtype, const void* A, const void* B, float* C, int M, int
 int ebc_transpose(int dtype, const void* in, void* out, int R, int C, long ld_out, ebc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * CLIP ViT-B/16 + deep VPT encoder: CLIP_EBC._forward_vpt (models/clip/model.py:142-189), whole
+ * CLIP ViT-B/16 and ViT-B/32 + deep VPT encoder: CLIP_EBC._forward_vpt (models/clip/model.py:142-189), whole
  * forward and dX-only backward (frozen encoder: gradients reach the VPT tokens only), one call each.
  * Weight pointers are device memory of `dtype` (matrices, nn.Linear [out, in] layout) or f32
  * (biases, LayerNorm, embeddings); wt_* are the transposed matrices [in, out] used by backward.
@@ -163,8 +163,8 @@ typedef struct {
 } EbcVitLayer;
 
 typedef struct {
-    int layers, width, heads, patch, num_vpt;
-    const void* w_patch;                        /* conv1.weight as [768, 3*16*16] */
+    int layers, width, heads, patch, num_vpt;   /* width 768, heads 12; patch 16 (ViT-B/16) or 32 (ViT-B/32) */
+    const void* w_patch;                        /* conv1.weight as [768, 3*patch*patch] */
     const float* cls;                           /* class_embedding [768] */
     const float* pos;                           /* positional_embedding [G+1, 768] for this input size */
     const float* ln_pre_g; const float* ln_pre_b; const float* ln_post_g; const float* ln_post_b;
@@ -173,7 +173,10 @@ typedef struct {
 
 /* Workspace (device bytes) holding the saved activations (training) or the ping-pong buffers. */
 size_t ebc_vit_workspace_bytes(int B, int H, int W, int layers, int num_vpt, int dtype, int training);
-/* image [B,3,H,W] f32 -> feat [B, (H/16)*(W/16), 768] f32 (= ln_post of the patch tokens, NHWC).
+/* The same for a given patch size (16 or 32; the call above means 16): the token grid is (H/patch) x (W/patch) and the
+ * patch rows are 3*patch*patch wide.  0 for a patch size the encoder does not take. */
+size_t ebc_vit_workspace_bytes_p(int B, int H, int W, int patch, int layers, int num_vpt, int dtype, int training);
+/* image [B,3,H,W] f32 (H, W multiples of w->patch) -> feat [B, (H/patch)*(W/patch), 768] f32 (= ln_post of the patch tokens, NHWC).
  * vpt: host array [layers] of device pointers ([num_vpt,768] f32, or [B,num_vpt,768] with
  * vpt_bstride = num_vpt*768 elements for per-crop prompts); vpt[l] == NULL for l > 0 keeps the
  * previous block's prompt outputs (shallow VPT, model.py:177-178). */
@@ -224,6 +227,10 @@ int ebc_head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, co
                  float* dbias, float* dscale, int P, int HW, int NB, int embed, void* workspace, size_t workspace_bytes,
                  ebc_stream_t stream);
 int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream);
+/* Patch rows of the patch-embedding GEMM (conv1 as im2col-GEMM, image_encoder.py:141): x [B,3,H,W] f32 ->
+ * out [B*(H/patch)*(W/patch), 3*patch*patch] of dtype, column k = c*patch*patch + kh*patch + kw (conv1.weight's
+ * order); patch % 4 == 0 and 3*patch*patch <= 4096 (one float4 a lane, up to 1024 lanes a row). */
+int ebc_im2col(int dtype, const float* x, void* out, int B, int H, int W, int patch, ebc_stream_t stream);
 
 /* Sliding-window evaluation (utils/eval_utils.py:26-96).  Tiles t = i*cols + j, rows/cols =
  * ceil((H-wh)/sh)+1, last row/column snapped to the border.
@@ -344,7 +351,7 @@ int ebc_bn_bwd_apply(int dtype, const void* gy, const void* mask_y, const void* 
 int ebc_dec_transpose3(int dtype, const void* xpad, void* xT3, int B, int H, int W, int C, ebc_stream_t stream);
 /* conv weight [N][C][3][3] f32 -> wk [N][3][3][C] (forward) and wf [C][3][3][N] (flipped, data gradient) */
 int ebc_dec_prep_weights(int dtype, const float* w, void* wk, void* wf, int N, int C, ebc_stream_t stream);
-/* dfeat [B][h][w][C] f32 = bilinear_up^T(g), g [B*H*W][C] (up = 1 or 2) */
+/* dfeat [B][h][w][C] f32 = bilinear_up^T(g), g [B*H*W][C] (up = 1, 2 or 4; other factors: EBC_E_UNSUPPORTED) */
 int ebc_dec_upsample_bwd(int dtype, const void* g, float* dfeat, int B, int h, int w, int C, int up,
                          ebc_stream_t stream);
 /* Flat-layout helpers of the ResNet-50 decoder Bottleneck (models/utils.py:306-363 with expansion 1, cfg [2048],
