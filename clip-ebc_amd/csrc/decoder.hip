@@ -1140,7 +1140,8 @@ extern "C" int ebc_bn_bwd_reduce(int dtype, const void* gy, const void* mask_y, 
                                  const float* rstd, const float* scale, const float* shift, double* sums, void* ws,
                                  size_t wsb, long P, int C, ebc_stream_t stream)
 {
-    if (!gy || !z || !mean || !rstd || !sums || C % 4 || (!mask_y && (!scale || !shift))) return EBC_E_ARG;
+    if (!gy || !z || !mean || !rstd || !sums || P <= 0 || C <= 0 || (!mask_y && (!scale || !shift))) return EBC_E_ARG;
+    if (C % 8) return EBC_E_UNSUPPORTED;          // one 8-channel vector per thread (bn_bwd_partial_kernel)
     const hipStream_t st = (hipStream_t)stream;
     switch (dtype) {
         case EBC_F32: return bn_bwd_reduce_t<float>(gy, mask_y, z, mean, rstd, scale, shift, sums, ws, wsb, P, C, st);
@@ -1280,8 +1281,9 @@ extern "C" int ebc_bn_bwd_reduce_finalize(int dtype, const void* gy, const void*
                                           float* dgamma, float* dbeta, float* coef, void* ws, size_t wsb, long P, int C,
                                           ebc_stream_t stream)
 {
-    if (!gy || !z || !mean || !rstd || !gamma || !coef || P <= 0 || C % 4 || (!mask_y && (!scale || !shift)))
+    if (!gy || !z || !mean || !rstd || !gamma || !coef || P <= 0 || C <= 0 || (!mask_y && (!scale || !shift)))
         return EBC_E_ARG;
+    if (C % 8) return EBC_E_UNSUPPORTED;          // as ebc_bn_bwd_reduce
     const BwdFin fin{gamma, dgamma, dbeta, coef};
     const hipStream_t st = (hipStream_t)stream;
     switch (dtype) {

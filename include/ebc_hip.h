@@ -294,8 +294,11 @@ int ebc_point_map(const float* points, const int* offsets, int B, int H, int W, 
  * Layouts (T = dtype): feat [B][h][w][C] f32; padded NHWC images [Q][C] T with Q = B*Hp*Wp;
  * z / dx / y [B*H*W][C] T; transposed images xT3 [3][C][Qs], dzT [N][Qs] T; conv weights
  * [N][3][3][C] T (forward) and [C][3][3][N] T (flipped, data gradient); dw [N][C][3][3] f32 (nn.Conv2d layout).
- * ebc_dec_geometry writes {Hp, Wp, G, kpi, Q, Qs}.  The workspace's first 16 KiB must be zero before
- * the first call (split-K arrival counters, re-armed by every call); it is stream-owned scratch. */
+ * ebc_dec_geometry writes {Hp, Wp, HWp, Kq, Q, Qs}: the padded image is Hp = H+2 rows of Wp >= W+2 positions
+ * (Wp a multiple of 8, at least 32), Q = B*Hp*Wp; HWp = H*W rounded up to 8 (at least 64) is one image's column
+ * count in dzT, Kq = B*HWp rounded up to 64 the columns ebc_bn_bwd_apply writes, Qs the row stride.
+ * The workspace's first 16 KiB must be zero before the first call (split-K arrival counters, re-armed by
+ * every call); it is stream-owned scratch. */
 int ebc_dec_geometry(int dtype, int B, int H, int W, int C, long* out6);
 size_t ebc_dec_workspace_bytes(int dtype, int B, int H, int W, int C, int N);
 /* xpad = zero-padded bilinear x`up` upsample of feat (H = h*up) */
@@ -336,7 +339,8 @@ int ebc_bn_relu_pad(int dtype, const void* z, const float* scale, const float* s
 /* y = relu(z*scale + shift + bilinear_up(feat)) */
 int ebc_bn_add_relu(int dtype, const void* z, const float* scale, const float* shift, const float* feat, int up,
                     void* y, int B, int H, int W, int C, ebc_stream_t stream);
-/* sums[2][C] f64 = (sum g, sum g*xhat), g = gy * relu'(mask_y, or z*scale+shift when mask_y == NULL) */
+/* sums[2][C] f64 = (sum g, sum g*xhat), g = gy * relu'(mask_y, or z*scale+shift when mask_y == NULL), relu'(0) = 0.
+ * P >= 1 rows (EBC_E_ARG otherwise); C a multiple of 8 up to 4096 (EBC_E_UNSUPPORTED otherwise) */
 int ebc_bn_bwd_reduce(int dtype, const void* gy, const void* mask_y, const void* z, const float* mean,
                       const float* rstd, const float* scale, const float* shift, double* sums, void* ws, size_t wsb,
                       long P, int C, ebc_stream_t stream);
