@@ -28,7 +28,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _lib
-from . import synthetic
+from . import resnet, synthetic
+from ._blocks import _conv3x3_bwd, _conv3x3_fwd, _dec_workspace, _geometry, _prep_1x1, _prep_3x3, _wgrad_rows
 from .text import CLIPTextEncoder, format_count, prompt_tokens
 
 WIDTH, HEADS, PATCH, EMBED = 768, 12, 16, 512
@@ -276,7 +277,6 @@ class _HeadFn(torch.autograd.Function):
             Y = (y.detach() if nhwc else y.detach().permute(0, 2, 3, 1)).to(cdtype).reshape(P, C).contiguous()
         E = weight.shape[0]                                        # CLIP joint width: 512 / 1024 (RN50)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            from .resnet import _prep_1x1
             Wc, Wt = _prep_1x1(L, weight, cdtype, st)              # [E, C] and [C, E], one launch
         else:
             Wc, Wt = weight.detach().reshape(E, C).to(cdtype).contiguous(), None
@@ -329,56 +329,15 @@ class _HeadFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- decoder
-_DEC_WS: Dict[Tuple[torch.device, int], Tensor] = {}
-
-
-def _dec_workspace(dev: torch.device, nbytes: int, slot: int = 0) -> Tensor:
-    """Scratch of the decoder calls on the caller's stream (slot 0: convolutions, slot 1: the weight-gradient
-    GEMMs, slot 2: the projection's dW GEMM); its first 16 KiB (split-K counters) start zeroed and every kernel
-    leaves them zero.  (The weight gradients on a side stream beside the data-gradient chain measured 2.7 %
-    slower per step, r01: the data-gradient chain is the critical path.)"""
-    ws = _DEC_WS.get((dev, slot))
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.zeros(max(nbytes, 1 << 20), device=dev, dtype=torch.uint8)
-        _DEC_WS[(dev, slot)] = ws
-    return ws
-
-
-def _wgrad_rows(L, dZ: Tensor, Y: Tensor, cdtype: torch.dtype, dev: torch.device, st) -> Tensor:
-    """dW [E, C] f32 = dZ^T Y for row matrices dZ [P, E], Y [P, C] (a 1x1 conv's weight gradient over
-    K = B*H*W pixels): both operands transposed to K-contiguous, then the split-K MFMA GEMM (K padded with
-    zero columns to the GEMM's K step when P is not a multiple of it)."""
-    dt = _lib.dtype_code(cdtype)
-    P, E = dZ.shape
-    C = Y.shape[1]
-    kstep = 32 if cdtype == torch.float32 else 64
-    Pp = -(-P // kstep) * kstep
-    alloc = torch.empty if Pp == P else torch.zeros
-    dZT = alloc(E, Pp, device=dev, dtype=cdtype)
-    YT = alloc(C, Pp, device=dev, dtype=cdtype)
-    _lib.check(L.ebc_transpose(dt, _lib.ptr(dZ), _lib.ptr(dZT), P, E, Pp, st), "ebc_transpose(dZ)")
-    _lib.check(L.ebc_transpose(dt, _lib.ptr(Y), _lib.ptr(YT), P, C, Pp, st), "ebc_transpose(Y)")
-    dW = torch.empty(E, C, device=dev, dtype=torch.float32)
-    ws = _dec_workspace(dev, L.ebc_gemm_wgrad_workspace_bytes(dt, E, C, Pp), slot=2)
-    _lib.check(L.ebc_gemm_wgrad(dt, _lib.ptr(dZT), _lib.ptr(YT), _lib.ptr(dW), E, C, Pp, _lib.ptr(ws), ws.numel(), st),
-               "ebc_gemm_wgrad")
-    return dW
-
-
 def _bn_group(bn: nn.Module):
-    """SyncBatchNorm (DDP, trainer.py:147): statistics are all-reduced over its process group."""
+    """SyncBatchNorm (DDP, trainer.py:147): statistics are all-reduced over its process group.  Every BatchNorm of
+    the block Functions asks this module attribute at call time (_blocks._bn_group): bench.py --syncbn-world1
+    replaces it."""
     if isinstance(bn, nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized():
         pg = bn.process_group or torch.distributed.group.WORLD
         if torch.distributed.get_world_size(pg) > 1:
             return pg
     return None
-
-
-def _bn_momentum(bn: nn.Module) -> float:
-    """nn.BatchNorm2d's exponential_average_factor (momentum None: cumulative average)."""
-    if bn.momentum is not None:
-        return float(bn.momentum)
-    return 1.0 / float(bn.num_batches_tracked.item())
 
 
 class DecoderMaskTap:
@@ -411,85 +370,31 @@ class _DecoderFn(torch.autograd.Function):
         if N != C or w2.shape[0] != C or C % 64:
             raise NotImplementedError("fused decoder: BasicBlock(C, C) with C % 64 == 0 only")
         dev, dt, st = feat.device, _lib.dtype_code(cdtype), _lib.stream(feat)
-        geo = (ctypes.c_long * 6)()
-        _lib.check(L.ebc_dec_geometry(dt, B, H, W, C, geo), "ebc_dec_geometry")
-        Q, Qs = geo[4], geo[5]
-        P = B * H * W
-        nbytes = L.ebc_dec_workspace_bytes(dt, B, H, W, C, N)
-        ws = _dec_workspace(dev, nbytes)
-        f32 = dict(device=dev, dtype=torch.float32)
-        xpad = torch.empty(Q, C, device=dev, dtype=cdtype)
+        geo = _geometry(L, dt, B, H, W, C, N)
+        P = geo.P
+        ws = _dec_workspace(dev, L.ebc_dec_workspace_bytes(dt, B, H, W, C, N))
+        xpad = torch.empty(geo.Q, C, device=dev, dtype=cdtype)
         _lib.check(L.ebc_dec_upsample_pad(dt, _lib.ptr(feat), _lib.ptr(xpad), B, h, w, C, up, st), "upsample_pad")
-        outs, wflip = [], []
-        inp = xpad
-        bns = (blk.bn1, blk.bn2)
-        for i, (wt, gm, bt) in enumerate(((w1, g1, b1), (w2, g2, b2))):
-            bn = bns[i]
-            wk = torch.empty(N, 3, 3, C, device=dev, dtype=cdtype)                 # [N][3][3][C]
-            wf = torch.empty(C, 3, 3, N, device=dev, dtype=cdtype)                 # [C][3][3][N], flipped
-            _lib.check(L.ebc_dec_prep_weights(dt, _lib.ptr(wt.detach().float().contiguous()), _lib.ptr(wk),
-                                              _lib.ptr(wf), N, C, st), "ebc_dec_prep_weights")
-            wflip.append(wf)
-            z = torch.empty(P, N, device=dev, dtype=cdtype)
-            use_batch = training or not bn.track_running_stats
-            pg = _bn_group(bn) if use_batch else None
-            # SyncBatchNorm: [sum | sum of squares | this rank's count] all-reduced in ONE f64 buffer, the total
-            # count read on device (count = -1), so ranks may hold different batch sizes (torch.nn.SyncBatchNorm
-            # gathers the per-rank counts the same way)
-            colsum = torch.empty(2 * N + (pg is not None), device=dev, dtype=torch.float64) if use_batch else None
-            fused_bn = use_batch and pg is None and training and bn.track_running_stats and bn.momentum is not None
-            if not fused_bn:
-                _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(inp), _lib.ptr(wk), _lib.ptr(z), _lib.ptr(colsum), None, None,
-                                             _lib.ptr(ws), ws.numel(), B, H, W, C, N, st), "ebc_conv3x3_fwd")
-            count = float(P)
-            if pg is not None:
-                colsum[2 * N].fill_(float(P))
-                torch.distributed.all_reduce(colsum, group=pg)
-                count = -1.0
-            mean, rstd, scale, shift = (torch.empty(N, **f32) for _ in range(4))
-            upd = use_batch and training and bn.track_running_stats
-            nbt = None                             # num_batches_tracked += 1 inside the finalize launch
-            if upd:
-                if bn.momentum is None:            # cumulative average: the factor needs the updated count now
-                    bn.num_batches_tracked.add_(1)
-                else:
-                    nbt = _lib.ptr(bn.num_batches_tracked)
-            mom = _bn_momentum(bn) if upd else 0.0
-            if fused_bn:
-                # no SyncBatchNorm exchange: the conv, then its column sums reduced and finalized in one launch
-                _lib.check(L.ebc_conv3x3_fwd_bn(dt, _lib.ptr(inp), _lib.ptr(wk), _lib.ptr(z), _lib.ptr(ws), ws.numel(),
-                                                B, H, W, C, N, float(bn.eps), mom, _lib.ptr(gm.detach()),
-                                                _lib.ptr(bt.detach()), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale),
-                                                _lib.ptr(shift), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var),
-                                                nbt, _lib.ptr(colsum), st), "ebc_conv3x3_fwd_bn")
-            else:
-                _lib.check(L.ebc_bn_finalize(_lib.ptr(colsum), count, float(bn.eps), mom, _lib.ptr(gm.detach()),
-                                             _lib.ptr(bt.detach()), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale),
-                                             _lib.ptr(shift), _lib.ptr(bn.running_mean) if (upd or not use_batch) else None,
-                                             _lib.ptr(bn.running_var) if (upd or not use_batch) else None, nbt, N, st),
-                           "ebc_bn_finalize")
-            outs.append((z, mean, rstd, scale, shift, count, pg, colsum))
-            if i == 0:
-                hpad = torch.empty(Q, N, device=dev, dtype=cdtype)
-                _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(z), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(hpad),
-                                             B, H, W, N, st), "ebc_bn_relu_pad")
-                inp = hpad
-        z2, _, _, scale2, shift2, _, _, _ = outs[1]
+        # conv1 -> bn1 -> relu, into the zero-padded conv2 input; conv2 -> bn2 (+ x) -> relu
+        wk1, wf1 = _prep_3x3(L, w1, cdtype, st)
+        s1 = _conv3x3_fwd(L, blk.bn1, xpad, wk1, geo, training, dt, ws, st, fuse=True)
+        hpad = torch.empty(geo.Q, N, device=dev, dtype=cdtype)
+        _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(s1.z), _lib.ptr(s1.scale), _lib.ptr(s1.shift), _lib.ptr(hpad),
+                                     B, H, W, N, st), "ebc_bn_relu_pad")
+        wk2, wf2 = _prep_3x3(L, w2, cdtype, st)
+        s2 = _conv3x3_fwd(L, blk.bn2, hpad, wk2, geo, training, dt, ws, st, fuse=True)
         y = torch.empty(B, H, W, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_add_relu(dt, _lib.ptr(z2), _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(feat), up,
+        _lib.check(L.ebc_bn_add_relu(dt, _lib.ptr(s2.z), _lib.ptr(s2.scale), _lib.ptr(s2.shift), _lib.ptr(feat), up,
                                      _lib.ptr(y), B, H, W, N, st), "ebc_bn_add_relu")
         if DecoderMaskTap.capture is not None:
-            Hp, Wp = geo[0], geo[1]
-            h1 = hpad.view(B, Hp, Wp, N)[:, 1:H + 1, 1:W + 1]
-            (z1, _, _, sc1, sh1), (z2, _, _, sc2, sh2) = (o[:5] for o in outs)
-            xu = xpad.view(B, Hp, Wp, C)[:, 1:H + 1, 1:W + 1].float().reshape(P, N)
-            DecoderMaskTap.capture.append(((h1 > 0).reshape(P, N), y > 0, z1.float() * sc1 + sh1,
-                                           (z2.float() * sc2 + sh2 + xu).view(B, H, W, N)))
-        ctx.save_for_backward(xpad, hpad, y, wflip[0], g1, wflip[1], g2)
-        from .resnet import flush_bn_counters
-        flush_bn_counters()                        # both BatchNorms' num_batches_tracked in one launch
-        ctx.outs = outs
-        ctx.meta = (B, h, w, H, W, C, N, up, cdtype, Q, Qs, P)
+            h1 = hpad.view(B, geo.Hp, geo.Wp, N)[:, 1:H + 1, 1:W + 1]
+            xu = xpad.view(B, geo.Hp, geo.Wp, C)[:, 1:H + 1, 1:W + 1].float().reshape(P, N)
+            DecoderMaskTap.capture.append(((h1 > 0).reshape(P, N), y > 0, s1.z.float() * s1.scale + s1.shift,
+                                           (s2.z.float() * s2.scale + s2.shift + xu).view(B, H, W, N)))
+        ctx.save_for_backward(xpad, hpad, y, wf1, g1, wf2, g2)
+        ctx.outs = (s1, s2)
+        ctx.geo = geo
+        ctx.meta = (B, h, w, H, W, C, N, up, cdtype, geo.Q, geo.Qs, P)
         return y
 
     @staticmethod
@@ -502,75 +407,24 @@ class _DecoderFn(torch.autograd.Function):
         L = _lib.lib()
         xpad, hpad, y, wf1, g1, wf2, g2 = ctx.saved_tensors
         B, h, w, H, W, C, N, up, cdtype, Q, Qs, P = ctx.meta
+        s1, s2 = ctx.outs
+        geo = ctx.geo
         dev, dt, st = y.device, _lib.dtype_code(cdtype), _lib.stream(y)
         gy = gy.to(cdtype).contiguous()
         nbytes = L.ebc_dec_workspace_bytes(dt, B, H, W, C, N)
         ws = _dec_workspace(dev, nbytes)
-        ws_w = _dec_workspace(dev, nbytes, 1)
-        f32 = dict(device=dev, dtype=torch.float32)
-        grads = []
-        dnext = gy                                    # gradient at the current BN output's ReLU
-        mask = y                                      # ReLU mask source (None: recompute from z)
-        ymask, mask1 = y, None
+        ws_w = _dec_workspace(dev, nbytes, 1)         # the weight gradients' own slot
+        ymask, mask1 = y, None                        # ReLU mask sources (None: recomputed from z)
         if DecoderMaskTap.replay:
             m1, m2 = DecoderMaskTap.replay.pop(0)[:2]
             mask1 = m1.to(cdtype).reshape(P, N).contiguous()
-            mask = ymask = m2.to(cdtype).reshape(B, H, W, N).contiguous()
-        for i in (1, 0):
-            z, mean, rstd, scale, shift, count, pg, colsum = ctx.outs[i]
-            gm = (g1, g2)[i]
-            dg, db, coef = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(3, N, **f32)
-            fused = pg is None and count == float(P)
-            if fused:
-                # no exchange: column sums and finalize in one launch (ebc_bn_bwd_reduce_finalize, count = P)
-                _lib.check(L.ebc_bn_bwd_reduce_finalize(dt, _lib.ptr(dnext), _lib.ptr(mask), _lib.ptr(z), _lib.ptr(mean),
-                                                        _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift),
-                                                        _lib.ptr(gm.detach()), _lib.ptr(dg), _lib.ptr(db), _lib.ptr(coef),
-                                                        _lib.ptr(ws), ws.numel(), P, N, st), "ebc_bn_bwd_reduce_finalize")
-            else:
-                sums = torch.empty(2 * N + (pg is not None), device=dev, dtype=torch.float64)
-                _lib.check(L.ebc_bn_bwd_reduce(dt, _lib.ptr(dnext), _lib.ptr(mask), _lib.ptr(z), _lib.ptr(mean),
-                                               _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(sums),
-                                               _lib.ptr(ws), ws.numel(), P, N, st), "ebc_bn_bwd_reduce")
-            if not fused and pg is not None:
-                # SyncBatchNorm backward (torch nn/modules/_functions.py, C5): d gamma / d beta come from THIS
-                # rank's sums (DDP then averages them over the ranks); the input gradient uses the all-reduced
-                # sums and the all-reduced count
-                _lib.check(L.ebc_bn_bwd_finalize(_lib.ptr(sums), float(P), _lib.ptr(gm.detach()), _lib.ptr(rstd),
-                                                 _lib.ptr(dg), _lib.ptr(db), _lib.ptr(coef), N, st), "ebc_bn_bwd_finalize")
-                torch.distributed.all_reduce(sums[: 2 * N], group=pg)     # sum_dy, sum_dy_xmu
-                sums[2 * N:].copy_(colsum[2 * N:])                          # the forward's all-reduced count
-                _lib.check(L.ebc_bn_bwd_finalize(_lib.ptr(sums), count, _lib.ptr(gm.detach()), _lib.ptr(rstd),
-                                                 None, None, _lib.ptr(coef), N, st), "ebc_bn_bwd_finalize(sync)")
-            elif not fused:
-                _lib.check(L.ebc_bn_bwd_finalize(_lib.ptr(sums), count, _lib.ptr(gm.detach()), _lib.ptr(rstd),
-                                                 _lib.ptr(dg), _lib.ptr(db), _lib.ptr(coef), N, st), "ebc_bn_bwd_finalize")
-            if colsum is None:                            # running statistics (eval mode): dz = gamma * rstd * g
-                coef[1:].zero_()
-            dzpad = torch.empty(Q, N, device=dev, dtype=cdtype)
-            dzT = torch.empty(N, Qs, device=dev, dtype=cdtype)
-            _lib.check(L.ebc_bn_bwd_apply(dt, _lib.ptr(dnext), _lib.ptr(mask), _lib.ptr(z), _lib.ptr(mean),
-                                          _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(coef),
-                                          _lib.ptr(dzpad), _lib.ptr(dzT), B, H, W, N, st), "ebc_bn_bwd_apply")
-            src = hpad if i == 1 else xpad                # the conv's input image
-            xT3 = torch.empty(3, C, Qs, device=dev, dtype=cdtype)
-            _lib.check(L.ebc_dec_transpose3(dt, _lib.ptr(src), _lib.ptr(xT3), B, H, W, C, st), "ebc_dec_transpose3")
-            dw = torch.empty(N, C, 3, 3, **f32)
-            _lib.check(L.ebc_conv3x3_wgrad(dt, _lib.ptr(dzT), _lib.ptr(xT3), _lib.ptr(dw), _lib.ptr(ws_w),
-                                           ws_w.numel(), B, H, W, C, N, st), "ebc_conv3x3_wgrad")
-            del xT3, dzT
-            wf = (wf1, wf2)[i]                                                    # [C][3][3][N]
-            dx = torch.empty(P, C, device=dev, dtype=cdtype)
-            # conv1's data gradient also takes the residual branch's gradient (gy through the final ReLU)
-            add = (_lib.ptr(gy), _lib.ptr(ymask)) if i == 0 else (None, None)
-            _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(dzpad), _lib.ptr(wf), _lib.ptr(dx), None, *add, _lib.ptr(ws),
-                                         ws.numel(), B, H, W, N, C, st), "ebc_conv3x3_fwd(dgrad)")
-            grads.append((dw, dg, db))
-            dnext, mask = dx, mask1
-        dfeat = torch.empty(B, h, w, C, **f32)
-        _lib.check(L.ebc_dec_upsample_bwd(dt, _lib.ptr(dnext), _lib.ptr(dfeat), B, h, w, C, up, st),
+            ymask = m2.to(cdtype).reshape(B, H, W, N).contiguous()
+        dh, dw2, dg2, db2 = _conv3x3_bwd(L, s2, g2, gy, ymask, hpad, wf2, geo, dt, ws, ws_w, st)
+        # conv1's data gradient also takes the residual branch's gradient (gy through the final ReLU)
+        dx, dw1, dg1, db1 = _conv3x3_bwd(L, s1, g1, dh, mask1, xpad, wf1, geo, dt, ws, ws_w, st, add_gy=gy, add_y=ymask)
+        dfeat = torch.empty(B, h, w, C, device=dev, dtype=torch.float32)
+        _lib.check(L.ebc_dec_upsample_bwd(dt, _lib.ptr(dx), _lib.ptr(dfeat), B, h, w, C, up, st),
                    "ebc_dec_upsample_bwd")
-        (dw2, dg2, db2), (dw1, dg1, db1) = grads
         ctx.outs = None
         return dfeat, dw1, dg1, db1, dw2, dg2, db2, None, None, None, None
 
@@ -600,10 +454,9 @@ class CLIP_EBC(nn.Module):
                                       "(SURVEY.md §8)")
         self.backbone = backbone
         if backbone == "resnet50":
-            from .resnet import Bottleneck, ModifiedResNet
             from .synthetic import RN50_CHANNELS, RN50_EMBED
             # models/clip/model.py:51-52 (trainable encoder), :83-95 (decoder cfg [2048] + projection)
-            self.image_encoder = ModifiedResNet(reduction=reduction).to(memory_format=torch.channels_last)
+            self.image_encoder = resnet.ModifiedResNet(reduction=reduction).to(memory_format=torch.channels_last)
             self.encoder_reduction = self.image_encoder.reduction
             self.reduction = self.encoder_reduction if reduction is None else reduction
             decoder_cfg = decoder_cfg or [RN50_CHANNELS]
@@ -611,7 +464,7 @@ class CLIP_EBC(nn.Module):
                 raise NotImplementedError("resnet50 decoder is Bottleneck [2048] (models/clip/model.py:237-238)")
             if self.encoder_reduction % self.reduction or self.encoder_reduction // self.reduction not in (1, 2):
                 raise NotImplementedError("resnet50: reduction must give a x1 / x2 bilinear adapt")
-            self.image_decoder = nn.Sequential(Bottleneck(RN50_CHANNELS, RN50_CHANNELS, expansion=1))
+            self.image_decoder = nn.Sequential(resnet.Bottleneck(RN50_CHANNELS, RN50_CHANNELS, expansion=1))
             embed = RN50_EMBED
         else:
             assert input_size is not None, "Expected input_size to be an integer, got None."
@@ -732,18 +585,16 @@ class CLIP_EBC(nn.Module):
     def _forward_resnet(self, x: Tensor, cdt: torch.dtype) -> Union[Tensor, Tuple[Tensor, Tensor]]:
         """models/clip/model.py:191-217 for the resnet50 backbone: the trainable ModifiedResNet (stem on PyTorch-ROCm,
         its 16 Bottlenecks on HIP), then the HIP Bottleneck decoder and head."""
-        from .resnet import _BottleneckFn, encoder_forward, flush_bn_counters
-        feat = encoder_forward(self.image_encoder, x, cdt, self.training)   # stem on MIOpen, 16 blocks on HIP
+        feat = resnet.encoder_forward(self.image_encoder, x, cdt, self.training)   # stem on MIOpen, 16 blocks on HIP
         feat = feat.float().contiguous()                                     # NHWC rows, f32
         up = self.encoder_reduction // self.reduction
         blk = self.image_decoder[0]
         with torch.autocast("cuda", enabled=False):
-            y = _BottleneckFn.apply(feat, blk.conv1.weight, blk.conv2.weight, blk.conv3.weight, blk.bn1.weight,
+            y = resnet._BottleneckFn.apply(feat, blk.conv1.weight, blk.conv2.weight, blk.conv3.weight, blk.bn1.weight,
                                     blk.bn1.bias, blk.bn2.weight, blk.bn2.bias, blk.bn3.weight, blk.bn3.bias, blk, up,
                                     cdt, self.training)
             logits, exp = _HeadFn.apply(y, self.projection.weight, self.projection.bias, self.logit_scale,
                                         self.text_features, self._anchors, cdt, True)
-        flush_bn_counters()
         return (logits, exp) if self.training else exp
 
     def forward(self, x: Tensor) -> Union[Tensor, Tuple[Tensor, Tensor]]:

@@ -16,14 +16,15 @@ except conv2's input, which is the zero-padded image the implicit-GEMM 3x3 conv 
 """
 from __future__ import annotations
 
-import ctypes
 from collections import OrderedDict
-from typing import Any, List, Optional, Tuple
+from typing import Any, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
+from ._blocks import (_conv1x1_bwd, _conv1x1_fwd, _conv3x3_bwd, _conv3x3_fwd, _dec_workspace, _geometry, _prep_1x1,
+                      _prep_3x3)
 
 
 # ----------------------------------------------------------------------------- encoder (PyTorch-ROCm)
@@ -128,116 +129,9 @@ class Bottleneck(nn.Module):
         self.downsample = nn.Identity()
 
 
-
-
-def _batch_norm_fwd(L, bn: nn.Module, colsum: Optional[Tensor], P: int, N: int, training: bool, dev, st, src=None):
-    """BatchNorm2d statistics -> (mean, rstd, scale, shift, count, group, colsum); SyncBatchNorm all-reduces
-    [sum | sum of squares | this rank's count] in one f64 buffer (as model._DecoderFn).  src = (dtype code, z, ws):
-    the statistics of z are taken here -- without an exchange, column sums and finalize in one launch
-    (ebc_bn_stats_finalize), else ebc_bn_stats into colsum first."""
-    from .model import _bn_group, _bn_momentum
-    f32 = dict(device=dev, dtype=torch.float32)
-    use_batch = colsum is not None
-    pg = _bn_group(bn) if use_batch else None
-    count = float(P)
-    fused = src is not None and use_batch and pg is None
-    if src is not None and use_batch and not fused:
-        dt, z, ws = src
-        _lib.check(L.ebc_bn_stats(dt, _lib.ptr(z), _lib.ptr(colsum), _lib.ptr(ws), ws.numel(), P, N, st), "ebc_bn_stats")
-    if pg is not None:
-        colsum[2 * N].fill_(float(P))
-        torch.distributed.all_reduce(colsum, group=pg)
-        count = -1.0
-    mean, rstd, scale, shift = (torch.empty(N, **f32) for _ in range(4))
-    upd = use_batch and training and bn.track_running_stats
-    nbt = None                                     # num_batches_tracked += 1 inside the finalize launch
-    if upd:
-        if bn.momentum is None:                    # cumulative average: the factor needs the updated count now
-            bn.num_batches_tracked.add_(1)
-        else:
-            nbt = _lib.ptr(bn.num_batches_tracked)
-    mom = _bn_momentum(bn) if upd else 0.0
-    if fused:
-        dt, z, ws = src
-        _lib.check(L.ebc_bn_stats_finalize(dt, _lib.ptr(z), _lib.ptr(ws), ws.numel(), P, N, float(bn.eps), mom,
-                                           _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()), _lib.ptr(mean),
-                                           _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift),
-                                           _lib.ptr(bn.running_mean) if upd else None,
-                                           _lib.ptr(bn.running_var) if upd else None, None, nbt, st), "ebc_bn_stats_finalize")
-        return mean, rstd, scale, shift, count, pg, colsum
-    _lib.check(L.ebc_bn_finalize(_lib.ptr(colsum) if use_batch else None, count, float(bn.eps), mom,
-                                 _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()), _lib.ptr(mean),
-                                 _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift),
-                                 _lib.ptr(bn.running_mean) if (upd or not use_batch) else None,
-                                 _lib.ptr(bn.running_var) if (upd or not use_batch) else None, nbt, N, st),
-               "ebc_bn_finalize")
-    return mean, rstd, scale, shift, count, pg, colsum
-
-
-def _batch_norm_bwd(L, gamma: Tensor, state, dnext: Tensor, mask: Optional[Tensor], z: Tensor, ws: Tensor, P: int,
-                    N: int, dev, st):
-    """Column sums of the BatchNorm backward -> (d gamma, d beta, coef); SyncBatchNorm: d gamma / d beta
-    from this rank's sums, the input-gradient coefficients from the all-reduced sums and count."""
-    mean, rstd, scale, shift, count, pg, colsum = state
-    f32 = dict(device=dev, dtype=torch.float32)
-    if pg is None:                    # no exchange: column sums and finalize in one launch
-        dg, db, coef = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(3, N, **f32)
-        _lib.check(L.ebc_bn_bwd_reduce_finalize(_lib.dtype_code(z.dtype), _lib.ptr(dnext), _lib.ptr(mask), _lib.ptr(z),
-                                                _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift),
-                                                _lib.ptr(gamma.detach()), _lib.ptr(dg), _lib.ptr(db), _lib.ptr(coef),
-                                                _lib.ptr(ws), ws.numel(), P, N, st), "ebc_bn_bwd_reduce_finalize")
-        return dg, db, _eval_coef(coef, colsum)
-    sums = torch.empty(2 * N + (pg is not None), device=dev, dtype=torch.float64)
-    _lib.check(L.ebc_bn_bwd_reduce(_lib.dtype_code(z.dtype), _lib.ptr(dnext), _lib.ptr(mask), _lib.ptr(z),
-                                   _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(sums),
-                                   _lib.ptr(ws), ws.numel(), P, N, st), "ebc_bn_bwd_reduce")
-    dg, db, coef = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(3, N, **f32)
-    g = _lib.ptr(gamma.detach())
-    _lib.check(L.ebc_bn_bwd_finalize(_lib.ptr(sums), float(P), g, _lib.ptr(rstd), _lib.ptr(dg), _lib.ptr(db),
-                                     _lib.ptr(coef), N, st), "ebc_bn_bwd_finalize")
-    if pg is not None:
-        torch.distributed.all_reduce(sums[: 2 * N], group=pg)
-        sums[2 * N:].copy_(colsum[2 * N:])
-        _lib.check(L.ebc_bn_bwd_finalize(_lib.ptr(sums), count, g, _lib.ptr(rstd), None, None, _lib.ptr(coef), N, st),
-                   "ebc_bn_bwd_finalize(sync)")
-    return dg, db, _eval_coef(coef, colsum)
-
-
-def _eval_coef(coef: Tensor, colsum: Optional[Tensor]) -> Tensor:
-    """BatchNorm normalised with its running statistics (eval mode, or track_running_stats with use of the running
-    estimates: no batch statistics, colsum None) has the input gradient gamma * rstd * g: the batch-mean terms
-    coef[1] = mean(g), coef[2] = mean(g * xhat) of the train-mode backward are zero (torch batch_norm_backward with
-    training=False); d gamma / d beta are the same column sums."""
-    if colsum is None:
-        coef[1:].zero_()
-    return coef
-
-
-def _prep_1x1(L, w: Tensor, cdtype: torch.dtype, st) -> Tuple[Tensor, Tensor]:
-    """1x1 conv weight [N, K, 1, 1] f32 -> ([N, K], [K, N]) in the compute dtype, one launch (ebc_prep_weights_1x1)."""
-    N, K = w.shape[0], w.shape[1]
-    wk = torch.empty(N, K, device=w.device, dtype=cdtype)
-    wt = torch.empty(K, N, device=w.device, dtype=cdtype)
-    _lib.check(L.ebc_prep_weights_1x1(_lib.dtype_code(cdtype), _lib.ptr(w.detach().float().contiguous()), _lib.ptr(wk),
-                                      _lib.ptr(wt), N, K, st), "ebc_prep_weights_1x1")
-    return wk, wt
-
-
-# BatchNorm num_batches_tracked increments of one forward, applied by ONE foreach launch (flush_bn_counters)
-# instead of one add kernel per BatchNorm (56 per clip_resnet50 step)
-_PENDING_NBT: List[Tensor] = []
-
-
-def flush_bn_counters() -> None:
-    if _PENDING_NBT:
-        torch._foreach_add_(_PENDING_NBT, 1)
-        _PENDING_NBT.clear()
-
-
 def _ws(L, dev, dt, B, H, W, C, N, P, Cmax):
     """Stream-owned scratch for one block: the 3x3 conv's (split-K counters + BN partials) and the flat BN kernels'
     column partials over P rows of up to Cmax channels."""
-    from .model import _dec_workspace
     rpb = 8 * max(1, 512 // max(1, Cmax // 8))
     need = max(L.ebc_dec_workspace_bytes(dt, B, H, W, C, N), 16384 + (-(-P // rpb)) * 8 * Cmax)
     return _dec_workspace(dev, need)
@@ -267,73 +161,46 @@ class _ResBlockFn(torch.autograd.Function):
         down = blk.downsample is not None
         dev, dt, st = x.device, _lib.dtype_code(cdtype), _lib.stream(x)
         ws = _ws(L, dev, dt, B, H, W, planes, planes, P, max(Cin, Cout, planes))
-        use_batch = training or not blk.bn1.track_running_stats
-        bns = (blk.bn1, blk.bn2, blk.bn3) + ((blk.downsample[2],) if down else ())
-        from .model import _bn_group
-
-        def colsum_for(bn):
-            return torch.empty(2 * bn.num_features + (_bn_group(bn) is not None), device=dev, dtype=torch.float64) \
-                if use_batch else None
-
-        def stats(z, bn, rows, C):
-            return _batch_norm_fwd(L, bn, colsum_for(bn), rows, C, training, dev, st, src=(dt, z, ws))
-
+        geo = _geometry(L, dt, B, H, W, planes, planes)
         W1, W1t = _prep_1x1(L, wts[0], cdtype, st)
         W3, W3t = _prep_1x1(L, wts[2], cdtype, st)
         Wd, Wdt = _prep_1x1(L, wts[3], cdtype, st) if down else (None, None)
-        geo = (ctypes.c_long * 6)()
-        _lib.check(L.ebc_dec_geometry(dt, B, H, W, planes, geo), "ebc_dec_geometry")
-        Q = geo[4]
-        wk2 = torch.empty(planes, 3, 3, planes, device=dev, dtype=cdtype)
-        wf2 = torch.empty(planes, 3, 3, planes, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_dec_prep_weights(dt, _lib.ptr(wts[1].detach().float().contiguous()), _lib.ptr(wk2), _lib.ptr(wf2),
-                                          planes, planes, st), "ebc_dec_prep_weights")
+        wk2, wf2 = _prep_3x3(L, wts[1], cdtype, st)
         # conv1 1x1 -> bn1 -> relu1, into the zero-padded conv2 input
-        z1 = torch.empty(P, planes, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(x), _lib.ptr(W1), _lib.ptr(z1), None, None, None, P, planes, Cin, st),
-                   "ebc_gemm(conv1)")
-        s1 = stats(z1, bns[0], P, planes)
-        h1pad = torch.empty(Q, planes, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(z1), _lib.ptr(s1[2]), _lib.ptr(s1[3]), _lib.ptr(h1pad), B, H, W, planes,
-                                     st), "ebc_bn_relu_pad")
+        s1 = _conv1x1_fwd(L, blk.bn1, x.view(P, Cin), W1, training, dt, ws, st)
+        h1pad = torch.empty(geo.Q, planes, device=dev, dtype=cdtype)
+        _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(s1.z), _lib.ptr(s1.scale), _lib.ptr(s1.shift), _lib.ptr(h1pad), B, H, W,
+                                     planes, st), "ebc_bn_relu_pad")
         # conv2 3x3 (BN statistics in the epilogue) -> bn2 -> relu2 -> avgpool(stride)
-        z2 = torch.empty(P, planes, device=dev, dtype=cdtype)
-        cs2 = colsum_for(bns[1])
-        _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(h1pad), _lib.ptr(wk2), _lib.ptr(z2), _lib.ptr(cs2), None, None,
-                                     _lib.ptr(ws), ws.numel(), B, H, W, planes, planes, st), "ebc_conv3x3_fwd")
-        s2 = _batch_norm_fwd(L, bns[1], cs2, P, planes, training, dev, st)
+        s2 = _conv3x3_fwd(L, blk.bn2, h1pad, wk2, geo, training, dt, ws, st)
         h2p = torch.empty(Po, planes, device=dev, dtype=cdtype)
         if s > 1:
-            _lib.check(L.ebc_bn_relu_avgpool(dt, _lib.ptr(z2), _lib.ptr(s2[2]), _lib.ptr(s2[3]), _lib.ptr(h2p), B, H, W,
-                                             planes, st), "ebc_bn_relu_avgpool")
+            _lib.check(L.ebc_bn_relu_avgpool(dt, _lib.ptr(s2.z), _lib.ptr(s2.scale), _lib.ptr(s2.shift), _lib.ptr(h2p),
+                                             B, H, W, planes, st), "ebc_bn_relu_avgpool")
         else:
-            _lib.check(L.ebc_bn_relu(dt, _lib.ptr(z2), _lib.ptr(s2[2]), _lib.ptr(s2[3]), _lib.ptr(h2p), P, planes, st),
-                       "ebc_bn_relu")
+            _lib.check(L.ebc_bn_relu(dt, _lib.ptr(s2.z), _lib.ptr(s2.scale), _lib.ptr(s2.shift), _lib.ptr(h2p), P, planes,
+                                     st), "ebc_bn_relu")
         # conv3 1x1 -> bn3
-        z3 = torch.empty(Po, Cout, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(h2p), _lib.ptr(W3), _lib.ptr(z3), None, None, None, Po, Cout, planes, st),
-                   "ebc_gemm(conv3)")
-        s3 = stats(z3, bns[2], Po, Cout)
+        s3 = _conv1x1_fwd(L, blk.bn3, h2p, W3, training, dt, ws, st)
         # identity: x, or avgpool(stride) -> 1x1 -> bn (downsample "-1", "0", "1")
-        xd = zd = sd = None
+        xd = sd = None
         if down:
             if s > 1:
                 xd = torch.empty(Po, Cin, device=dev, dtype=cdtype)
                 _lib.check(L.ebc_avgpool2(dt, dt, _lib.ptr(x), _lib.ptr(xd), B, H, W, Cin, st), "ebc_avgpool2")
             else:
                 xd = x.view(P, Cin)
-            zd = torch.empty(Po, Cout, device=dev, dtype=cdtype)
-            _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(xd), _lib.ptr(Wd), _lib.ptr(zd), None, None, None, Po, Cout, Cin, st),
-                       "ebc_gemm(downsample)")
-            sd = stats(zd, bns[3], Po, Cout)
+            sd = _conv1x1_fwd(L, blk.downsample[2], xd, Wd, training, dt, ws, st)
         y = torch.empty(B, Ho, Wo, Cout, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_add_relu_flat(dt, _lib.ptr(z3), _lib.ptr(s3[2]), _lib.ptr(s3[3]),
-                                          _lib.ptr(zd if down else x), _lib.ptr(sd[2]) if down else None,
-                                          _lib.ptr(sd[3]) if down else None, _lib.ptr(y), Po, Cout, st), "ebc_bn_add_relu_flat")
-        ctx.save_for_backward(x, z1, h1pad, z2, h2p, z3, y, W1t, wf2, W3t, *(() if not down else (xd, zd, Wdt)))
+        _lib.check(L.ebc_bn_add_relu_flat(dt, _lib.ptr(s3.z), _lib.ptr(s3.scale), _lib.ptr(s3.shift),
+                                          _lib.ptr(sd.z if down else x), _lib.ptr(sd.scale) if down else None,
+                                          _lib.ptr(sd.shift) if down else None, _lib.ptr(y), Po, Cout, st),
+                   "ebc_bn_add_relu_flat")
+        ctx.save_for_backward(x, h1pad, h2p, y, W1t, wf2, W3t, *((xd, Wdt) if down else ()))
         ctx.states = (s1, s2, s3, sd)
-        ctx.gammas = tuple(bn.weight for bn in bns)
-        ctx.meta = (B, H, W, Cin, s, Ho, Wo, P, Po, planes, Cout, down, cdtype, x.dtype)
+        ctx.gammas = (blk.bn1.weight, blk.bn2.weight, blk.bn3.weight, blk.downsample[2].weight if down else None)
+        ctx.geo = geo
+        ctx.meta = (Cin, s, Po, Cout, down, cdtype, x.dtype)
         return y
 
     @staticmethod
@@ -343,49 +210,26 @@ class _ResBlockFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, gy):
-        from .model import _wgrad_rows
         L = _lib.lib()
-        B, H, W, Cin, s, Ho, Wo, P, Po, planes, Cout, down, cdtype, xdt = ctx.meta
+        Cin, s, Po, Cout, down, cdtype, xdt = ctx.meta
+        geo = ctx.geo
+        B, H, W, planes, P = geo.B, geo.H, geo.W, geo.C, geo.P
         saved = ctx.saved_tensors
-        x, z1, h1pad, z2, h2p, z3, y, W1t, wf2, W3t = saved[:10]
-        xd, zd, Wdt = saved[10:] if down else (None, None, None)
+        x, h1pad, h2p, y, W1t, wf2, W3t = saved[:7]
+        xd, Wdt = saved[7:] if down else (None, None)
         s1, s2, s3, sd = ctx.states
-        g1, g2, g3 = ctx.gammas[:3]
+        g1, g2, g3, gd = ctx.gammas
         dev, dt, st = y.device, _lib.dtype_code(cdtype), _lib.stream(y)
         gy = gy.to(cdtype).contiguous().view(Po, Cout)
         ws = _ws(L, dev, dt, B, H, W, planes, planes, P, max(Cin, Cout, planes))
-        geo = (ctypes.c_long * 6)()
-        _lib.check(L.ebc_dec_geometry(dt, B, H, W, planes, geo), "ebc_dec_geometry")
-        Q, Qs = geo[4], geo[5]
         f32 = dict(device=dev, dtype=torch.float32)
-
-        def apply_flat(g, mask, z, st_, coef, gmask=None):
-            dz = torch.empty(z.shape, device=dev, dtype=cdtype)
-            _lib.check(L.ebc_bn_bwd_apply_flat(dt, _lib.ptr(g), _lib.ptr(mask), _lib.ptr(z), _lib.ptr(st_[0]),
-                                               _lib.ptr(st_[1]), _lib.ptr(st_[2]), _lib.ptr(st_[3]), _lib.ptr(coef),
-                                               _lib.ptr(dz), _lib.ptr(gmask), z.shape[0], z.shape[1], st),
-                       "ebc_bn_bwd_apply_flat")
-            return dz
-
-        # bn3 (+ relu3 through y); without a downsample the identity's gradient is g = gy * (y > 0) itself (f32)
-        dg3, db3, coef3 = _batch_norm_bwd(L, g3, s3, gy, y, z3, ws, Po, Cout, dev, st)
+        # bn3 (+ relu3 through y) -> conv3; without a downsample the identity's gradient is g = gy * (y > 0) itself (f32)
         gid = None if down else torch.empty(Po, Cout, **f32)
-        dz3 = apply_flat(gy, y, z3, s3, coef3, gid)
-        dw3 = _wgrad_rows(L, dz3, h2p, cdtype, dev, st)
-        dh2p = torch.empty(Po, planes, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(dz3), _lib.ptr(W3t), _lib.ptr(dh2p), None, None, None,
-                              Po, planes, Cout, st), "ebc_gemm(conv3 dX)")
-        del dz3
+        dh2p, dw3, dg3, db3 = _conv1x1_bwd(L, s3, g3, gy, y, h2p, W3t, dt, ws, st, gmask=gid)
         dwd = dgd = dbd = None
         if down:
             # downsample bn (same masked gradient) -> 1x1 -> avgpool: the identity's input gradient, f32
-            dgd, dbd, coefd = _batch_norm_bwd(L, ctx.gammas[3], sd, gy, y, zd, ws, Po, Cout, dev, st)
-            dzd = apply_flat(gy, y, zd, sd, coefd)
-            dwd = _wgrad_rows(L, dzd, xd, cdtype, dev, st)
-            dxd = torch.empty(Po, Cin, **f32)
-            _lib.check(L.ebc_gemm(dt, 0, 1, _lib.ptr(dzd), _lib.ptr(Wdt), _lib.ptr(dxd), None, None, None,
-                                  Po, Cin, Cout, st), "ebc_gemm(downsample dX)")
-            del dzd
+            dxd, dwd, dgd, dbd = _conv1x1_bwd(L, sd, gd, gy, y, xd, Wdt, dt, ws, st, out_f32=True)
             if s > 1:
                 gid = torch.empty(P, Cin, **f32)
                 _lib.check(L.ebc_avgpool2_bwd(_lib.EBC_F32, _lib.EBC_F32, _lib.ptr(dxd), _lib.ptr(gid), B, H, W, Cin, st),
@@ -400,31 +244,11 @@ class _ResBlockFn(torch.autograd.Function):
             del dh2p
         else:
             dh2 = dh2p
-        dg2, db2, coef2 = _batch_norm_bwd(L, g2, s2, dh2, None, z2, ws, P, planes, dev, st)
-        dz2pad = torch.empty(Q, planes, device=dev, dtype=cdtype)
-        dz2T = torch.empty(planes, Qs, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_bwd_apply(dt, _lib.ptr(dh2), None, _lib.ptr(z2), _lib.ptr(s2[0]), _lib.ptr(s2[1]),
-                                      _lib.ptr(s2[2]), _lib.ptr(s2[3]), _lib.ptr(coef2), _lib.ptr(dz2pad), _lib.ptr(dz2T),
-                                      B, H, W, planes, st), "ebc_bn_bwd_apply(bn2)")
+        dh1, dw2, dg2, db2 = _conv3x3_bwd(L, s2, g2, dh2, None, h1pad, wf2, geo, dt, ws, ws, st)
         del dh2
-        xT3 = torch.empty(3, planes, Qs, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_dec_transpose3(dt, _lib.ptr(h1pad), _lib.ptr(xT3), B, H, W, planes, st), "ebc_dec_transpose3")
-        dw2 = torch.empty(planes, planes, 3, 3, **f32)
-        _lib.check(L.ebc_conv3x3_wgrad(dt, _lib.ptr(dz2T), _lib.ptr(xT3), _lib.ptr(dw2), _lib.ptr(ws), ws.numel(),
-                                       B, H, W, planes, planes, st), "ebc_conv3x3_wgrad")
-        del xT3, dz2T
-        dh1 = torch.empty(P, planes, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(dz2pad), _lib.ptr(wf2), _lib.ptr(dh1), None, None, None, _lib.ptr(ws),
-                                     ws.numel(), B, H, W, planes, planes, st), "ebc_conv3x3_fwd(dgrad)")
-        del dz2pad
         # bn1 (ReLU mask recomputed from z1) -> conv1: dx = dz1 W1 + the identity's gradient
-        dg1, db1, coef1 = _batch_norm_bwd(L, g1, s1, dh1, None, z1, ws, P, planes, dev, st)
-        dz1 = apply_flat(dh1, None, z1, s1, coef1)
-        del dh1
-        dw1 = _wgrad_rows(L, dz1, x.view(P, Cin), cdtype, dev, st)
-        dx = torch.empty(B, H, W, Cin, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 2, 0, _lib.ptr(dz1), _lib.ptr(W1t), _lib.ptr(dx), None, _lib.ptr(gid),
-                              None, P, Cin, planes, st), "ebc_gemm(conv1 dX + identity)")
+        dx, dw1, dg1, db1 = _conv1x1_bwd(L, s1, g1, dh1, None, x.view(P, Cin), W1t, dt, ws, st, resid=gid)
+        dx = dx.view(B, H, W, Cin)
         ctx.states = None
         return (dx.to(xdt) if xdt != cdtype else dx, dw1.view(planes, Cin, 1, 1), dw2, dw3.view(Cout, planes, 1, 1),
                 None if dwd is None else dwd.view(Cout, Cin, 1, 1), dg1, db1, dg2, db2, dg3, db3, dgd, dbd,
@@ -448,7 +272,6 @@ def encoder_forward(enc: "ModifiedResNet", x: Tensor, cdtype: torch.dtype, train
                                       None if d is None else d[1].weight, blk.bn1.weight, blk.bn1.bias, blk.bn2.weight,
                                       blk.bn2.bias, blk.bn3.weight, blk.bn3.bias, None if d is None else d[2].weight,
                                       None if d is None else d[2].bias, blk, cdtype, training)
-    flush_bn_counters()
     return h
 
 
@@ -464,7 +287,6 @@ class _BottleneckFn(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, feat, wts, gammas, blk, up, cdtype, training):
-        from .model import _bn_group, _dec_workspace
         L = _lib.lib()
         feat = feat.detach().contiguous()
         B, h, w, C = feat.shape
@@ -473,55 +295,33 @@ class _BottleneckFn(torch.autograd.Function):
         if N != C or C % 256:
             raise NotImplementedError("fused Bottleneck decoder: C == N, C % 256 == 0")
         dev, dt, st = feat.device, _lib.dtype_code(cdtype), _lib.stream(feat)
-        P = B * H * W
-        geo = (ctypes.c_long * 6)()
-        _lib.check(L.ebc_dec_geometry(dt, B, H, W, C, geo), "ebc_dec_geometry")
-        Q = geo[4]
+        geo = _geometry(L, dt, B, H, W, C, N)
+        P = geo.P
         ws = _dec_workspace(dev, L.ebc_dec_workspace_bytes(dt, B, H, W, C, N))
-        use_batch = training or not blk.bn1.track_running_stats
-        bns = (blk.bn1, blk.bn2, blk.bn3)
-
-        def colsum_for(bn):
-            if not use_batch:
-                return None
-            return torch.empty(2 * N + (_bn_group(bn) is not None), device=dev, dtype=torch.float64)
-
         x = torch.empty(P, C, device=dev, dtype=cdtype)
         _lib.check(L.ebc_dec_upsample(dt, _lib.ptr(feat), _lib.ptr(x), B, h, w, C, up, st), "ebc_dec_upsample")
         W1, W1t = _prep_1x1(L, wts[0], cdtype, st)
         W3, W3t = _prep_1x1(L, wts[2], cdtype, st)
-        wk2 = torch.empty(N, 3, 3, N, device=dev, dtype=cdtype)
-        wf2 = torch.empty(N, 3, 3, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_dec_prep_weights(dt, _lib.ptr(wts[1].detach().float().contiguous()), _lib.ptr(wk2),
-                                          _lib.ptr(wf2), N, N, st), "ebc_dec_prep_weights")
+        wk2, wf2 = _prep_3x3(L, wts[1], cdtype, st)
         # conv1 (1x1) + bn1 + relu -> padded conv2 input
-        z1 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(x), _lib.ptr(W1), _lib.ptr(z1), None, None, None, P, N, C, st),
-                   "ebc_gemm(conv1)")
-        s1 = _batch_norm_fwd(L, bns[0], colsum_for(bns[0]), P, N, training, dev, st, src=(dt, z1, ws))
-        h1pad = torch.empty(Q, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(z1), _lib.ptr(s1[2]), _lib.ptr(s1[3]), _lib.ptr(h1pad), B, H, W, N,
-                                     st), "ebc_bn_relu_pad")
+        s1 = _conv1x1_fwd(L, blk.bn1, x, W1, training, dt, ws, st)
+        h1pad = torch.empty(geo.Q, N, device=dev, dtype=cdtype)
+        _lib.check(L.ebc_bn_relu_pad(dt, _lib.ptr(s1.z), _lib.ptr(s1.scale), _lib.ptr(s1.shift), _lib.ptr(h1pad), B, H, W,
+                                     N, st), "ebc_bn_relu_pad")
         # conv2 (3x3, BN statistics in the GEMM epilogue) + bn2 + relu
-        z2 = torch.empty(P, N, device=dev, dtype=cdtype)
-        cs2 = colsum_for(bns[1])
-        _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(h1pad), _lib.ptr(wk2), _lib.ptr(z2), _lib.ptr(cs2), None, None,
-                                     _lib.ptr(ws), ws.numel(), B, H, W, N, N, st), "ebc_conv3x3_fwd")
-        s2 = _batch_norm_fwd(L, bns[1], cs2, P, N, training, dev, st)
+        s2 = _conv3x3_fwd(L, blk.bn2, h1pad, wk2, geo, training, dt, ws, st)
         h2 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_relu(dt, _lib.ptr(z2), _lib.ptr(s2[2]), _lib.ptr(s2[3]), _lib.ptr(h2), P, N, st),
+        _lib.check(L.ebc_bn_relu(dt, _lib.ptr(s2.z), _lib.ptr(s2.scale), _lib.ptr(s2.shift), _lib.ptr(h2), P, N, st),
                    "ebc_bn_relu")
         # conv3 (1x1) + bn3 + identity + relu
-        z3 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(h2), _lib.ptr(W3), _lib.ptr(z3), None, None, None, P, N, N, st),
-                   "ebc_gemm(conv3)")
-        s3 = _batch_norm_fwd(L, bns[2], colsum_for(bns[2]), P, N, training, dev, st, src=(dt, z3, ws))
+        s3 = _conv1x1_fwd(L, blk.bn3, h2, W3, training, dt, ws, st)
         y = torch.empty(B, H, W, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_add_relu(dt, _lib.ptr(z3), _lib.ptr(s3[2]), _lib.ptr(s3[3]), _lib.ptr(feat), up, _lib.ptr(y),
-                                     B, H, W, N, st), "ebc_bn_add_relu")
-        ctx.save_for_backward(x, z1, h1pad, z2, h2, z3, y, W1t, wf2, W3t, *gammas)
+        _lib.check(L.ebc_bn_add_relu(dt, _lib.ptr(s3.z), _lib.ptr(s3.scale), _lib.ptr(s3.shift), _lib.ptr(feat), up,
+                                     _lib.ptr(y), B, H, W, N, st), "ebc_bn_add_relu")
+        ctx.save_for_backward(x, h1pad, h2, y, W1t, wf2, W3t, *gammas)
         ctx.states = (s1, s2, s3)
-        ctx.meta = (B, h, w, H, W, C, N, up, cdtype, P)
+        ctx.geo = geo
+        ctx.meta = (h, w, up, cdtype)
         return y
 
     @staticmethod
@@ -531,62 +331,23 @@ class _BottleneckFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, gy):
-        from .model import _dec_workspace, _wgrad_rows
         L = _lib.lib()
-        x, z1, h1pad, z2, h2, z3, y, W1t, wf2, W3t, g1, g2, g3 = ctx.saved_tensors
+        x, h1pad, h2, y, W1t, wf2, W3t, g1, g2, g3 = ctx.saved_tensors
         s1, s2, s3 = ctx.states
-        B, h, w, H, W, C, N, up, cdtype, P = ctx.meta
+        h, w, up, cdtype = ctx.meta
+        geo = ctx.geo
+        B, H, W, C, N, P = geo.B, geo.H, geo.W, geo.C, geo.N, geo.P
         dev, dt, st = y.device, _lib.dtype_code(cdtype), _lib.stream(y)
         gy = gy.to(cdtype).contiguous().view(P, N)
         ws = _dec_workspace(dev, L.ebc_dec_workspace_bytes(dt, B, H, W, C, N))
-        geo = (ctypes.c_long * 6)()
-        _lib.check(L.ebc_dec_geometry(dt, B, H, W, C, geo), "ebc_dec_geometry")
-        Q, Qs = geo[4], geo[5]
-        # bn3 (+ relu through the block output y); the identity branch keeps g = gy * (y > 0) in f32
-        dg3, db3, coef3 = _batch_norm_bwd(L, g3, s3, gy, y, z3, ws, P, N, dev, st)
-        dz3 = torch.empty(P, N, device=dev, dtype=cdtype)
+        # bn3 (+ relu through the block output y) -> conv3; the identity branch keeps g = gy * (y > 0) in f32
         gid = torch.empty(P, C, device=dev, dtype=torch.float32)
-        mean3, rstd3, sc3, sh3 = s3[:4]
-        _lib.check(L.ebc_bn_bwd_apply_flat(dt, _lib.ptr(gy), _lib.ptr(y), _lib.ptr(z3), _lib.ptr(mean3), _lib.ptr(rstd3),
-                                           _lib.ptr(sc3), _lib.ptr(sh3), _lib.ptr(coef3), _lib.ptr(dz3), _lib.ptr(gid),
-                                           P, N, st), "ebc_bn_bwd_apply_flat(bn3)")
-        # conv3: dW3 = dz3^T h2, dh2 = dz3 W3
-        dw3 = _wgrad_rows(L, dz3, h2, cdtype, dev, st)
-        dh2 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_gemm(dt, 0, 0, _lib.ptr(dz3), _lib.ptr(W3t), _lib.ptr(dh2), None, None, None,
-                              P, N, N, st), "ebc_gemm(conv3 dX)")
-        del dz3
-        # bn2 (+ relu through h2) -> padded / transposed dz2 for the 3x3 conv's gradients
-        dg2, db2, coef2 = _batch_norm_bwd(L, g2, s2, dh2, h2, z2, ws, P, N, dev, st)
-        mean2, rstd2, sc2, sh2 = s2[:4]
-        dz2pad = torch.empty(Q, N, device=dev, dtype=cdtype)
-        dz2T = torch.empty(N, Qs, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_bwd_apply(dt, _lib.ptr(dh2), _lib.ptr(h2), _lib.ptr(z2), _lib.ptr(mean2), _lib.ptr(rstd2),
-                                      _lib.ptr(sc2), _lib.ptr(sh2), _lib.ptr(coef2), _lib.ptr(dz2pad), _lib.ptr(dz2T),
-                                      B, H, W, N, st), "ebc_bn_bwd_apply(bn2)")
+        dh2, dw3, dg3, db3 = _conv1x1_bwd(L, s3, g3, gy, y, h2, W3t, dt, ws, st, gmask=gid)
+        # bn2 (+ relu through h2) -> conv2's gradients
+        dh1, dw2, dg2, db2 = _conv3x3_bwd(L, s2, g2, dh2, h2, h1pad, wf2, geo, dt, ws, ws, st)
         del dh2
-        xT3 = torch.empty(3, N, Qs, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_dec_transpose3(dt, _lib.ptr(h1pad), _lib.ptr(xT3), B, H, W, N, st), "ebc_dec_transpose3")
-        dw2 = torch.empty(N, N, 3, 3, device=dev, dtype=torch.float32)
-        _lib.check(L.ebc_conv3x3_wgrad(dt, _lib.ptr(dz2T), _lib.ptr(xT3), _lib.ptr(dw2), _lib.ptr(ws), ws.numel(),
-                                       B, H, W, N, N, st), "ebc_conv3x3_wgrad")
-        del xT3, dz2T
-        dh1 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_conv3x3_fwd(dt, _lib.ptr(dz2pad), _lib.ptr(wf2), _lib.ptr(dh1), None, None, None, _lib.ptr(ws),
-                                     ws.numel(), B, H, W, N, N, st), "ebc_conv3x3_fwd(dgrad)")
-        del dz2pad
-        # bn1 (ReLU mask recomputed from z1)
-        dg1, db1, coef1 = _batch_norm_bwd(L, g1, s1, dh1, None, z1, ws, P, N, dev, st)
-        mean1, rstd1, sc1, sh1 = s1[:4]
-        dz1 = torch.empty(P, N, device=dev, dtype=cdtype)
-        _lib.check(L.ebc_bn_bwd_apply_flat(dt, _lib.ptr(dh1), None, _lib.ptr(z1), _lib.ptr(mean1), _lib.ptr(rstd1),
-                                           _lib.ptr(sc1), _lib.ptr(sh1), _lib.ptr(coef1), _lib.ptr(dz1), None, P, N, st),
-                   "ebc_bn_bwd_apply_flat(bn1)")
-        del dh1
-        # conv1: dW1 = dz1^T x, dx = dz1 W1 + the identity branch's gradient (f32, in place over gid)
-        dw1 = _wgrad_rows(L, dz1, x, cdtype, dev, st)
-        _lib.check(L.ebc_gemm(dt, 2, 1, _lib.ptr(dz1), _lib.ptr(W1t), _lib.ptr(gid), None,
-                              _lib.ptr(gid), None, P, C, N, st), "ebc_gemm(conv1 dX + identity)")
+        # bn1 (ReLU mask recomputed from z1) -> conv1: dx = dz1 W1 + the identity branch's gradient (f32, in place over gid)
+        _, dw1, dg1, db1 = _conv1x1_bwd(L, s1, g1, dh1, None, x, W1t, dt, ws, st, resid=gid, out=gid, out_f32=True)
         dfeat = torch.empty(B, h, w, C, device=dev, dtype=torch.float32)
         _lib.check(L.ebc_dec_upsample_bwd(_lib.EBC_F32, _lib.ptr(gid), _lib.ptr(dfeat), B, h, w, C, up, st),
                    "ebc_dec_upsample_bwd")

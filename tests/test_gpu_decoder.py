@@ -28,21 +28,23 @@ PRE_TOL = 5e-5
 FLIP_RATE = 5e-6
 
 
-def _ref(feat, w1, g1, b1, w2, g2, b2, up, rm, rv, training, masks=None, pre=None):
+def _ref(feat, w1, g1, b1, w2, g2, b2, up, rm, rv, training, masks=None, pre=None, momentum=0.1):
     """The reference block in f64.  masks = (m1, m2) replaces the two ReLUs by products with those {0, 1} masks
     (NCHW): the f64 restatement then follows the HIP forward's own ReLU decisions, so a pre-activation that lies
     within f32 resolution of zero (and took the other sign in the f32 forward) cannot move the comparison.
-    pre: a list that receives the two f64 pre-activations (NCHW)."""
+    pre: a list that receives the two f64 pre-activations (NCHW).  rm / rv entries None: a BatchNorm without
+    running statistics; momentum: this step's exponential average factor (1 / num_batches_tracked for a BatchNorm
+    built with momentum None)."""
     x = feat.permute(0, 3, 1, 2)
     if up > 1:
         x = F.interpolate(x, scale_factor=up, mode="bilinear")
     o = F.conv2d(x, w1, padding=1)
-    o = F.batch_norm(o, rm[0], rv[0], g1, b1, training, 0.1, 1e-5)
+    o = F.batch_norm(o, rm[0], rv[0], g1, b1, training, momentum, 1e-5)
     if pre is not None:
         pre.append(o.detach())
     o = F.relu(o) if masks is None else o * masks[0]
     o = F.conv2d(o, w2, padding=1)
-    o = F.batch_norm(o, rm[1], rv[1], g2, b2, training, 0.1, 1e-5) + x
+    o = F.batch_norm(o, rm[1], rv[1], g2, b2, training, momentum, 1e-5) + x
     if pre is not None:
         pre.append(o.detach())
     return (F.relu(o) if masks is None else o * masks[1]).permute(0, 2, 3, 1)
@@ -68,8 +70,8 @@ def _hip_pre1(y):
     """bn1's pre-activation as the HIP forward formed it (z1 * scale + shift, f32 operands, NCHW f64)."""
     node = y.grad_fn
     B, h, w, H, W, C, N = node.meta[:7]
-    z, _, _, scale, shift = node.outs[0][:5]
-    pre = z.double() * scale.double() + shift.double()
+    s1 = node.outs[0]
+    pre = s1.z.double() * s1.scale.double() + s1.shift.double()
     return pre.view(B, H, W, N).permute(0, 3, 1, 2).cpu()
 
 
@@ -220,6 +222,77 @@ def test_decoder_eval_backward(dtype):
                     params):
         assert rel_l2(p.grad.cpu().numpy(), r.grad.numpy()) < GTOL[dtype], p.shape
     assert int(blk.bn1.num_batches_tracked) == 0
+
+
+def _decoder_args(blk):
+    return (blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight, blk.bn2.weight, blk.bn2.bias)
+
+
+def _assert_decoder_grads(fd, blk, fr, params):
+    assert rel_l2(fd.grad.cpu().numpy(), fr.grad.numpy()) < GTOL[torch.float32]
+    for p, r in zip(_decoder_args(blk), params):
+        assert rel_l2(p.grad.cpu().numpy(), r.grad.numpy()) < GTOL[torch.float32], p.shape
+
+
+def test_decoder_momentum_none_cumulative_average():
+    """BatchNorm2d(momentum=None): two training steps leave the cumulative average of the batch statistics in the
+    running buffers (factor 1, then 1/2) and num_batches_tracked == 2; step two's gradients match the reference."""
+    from ebc_amd.model import _DecoderFn
+    B, h, C, up, dtype = 2, 7, 128, 1, torch.float32
+    blk = _block(C)
+    for bn in (blk.bn1, blk.bn2):
+        bn.momentum = None
+    g = torch.Generator().manual_seed(6)
+    feats = [torch.randn(B, h, h, C, generator=g) for _ in range(2)]
+    gy = torch.randn(B, h * up, h * up, C, generator=g)
+    params, rm, rv = _f64_params(blk)
+    for k, feat in enumerate(feats, 1):
+        for p in params:
+            p.grad = None
+        fr = feat.double().requires_grad_()
+        yr = _ref(fr, *params, up, rm, rv, True, momentum=1.0 / k)
+        (yr * gy.double()).sum().backward()
+    blk = blk.cuda().train()
+    for feat in feats:
+        blk.zero_grad(set_to_none=True)
+        fd = feat.cuda().requires_grad_()
+        y = _DecoderFn.apply(fd, *_decoder_args(blk), blk, up, dtype, True)
+        (y * gy.cuda()).sum().backward()
+    assert rel_l2(y.detach().cpu().numpy(), yr.detach().numpy()) < TOL[dtype]
+    for bn, m, v in zip((blk.bn1, blk.bn2), rm, rv):
+        assert rel_l2(bn.running_mean.cpu().numpy(), m.numpy()) < TOL[dtype]
+        assert rel_l2(bn.running_var.cpu().numpy(), v.numpy()) < TOL[dtype]
+        assert int(bn.num_batches_tracked) == 2
+    _assert_decoder_grads(fd, blk, fr, params)
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_decoder_without_running_stats(training):
+    """BatchNorm2d(track_running_stats=False) has no running buffers: train and eval mode both normalise with the
+    batch statistics, as F.batch_norm(..., None, None, training=True)."""
+    from ebc_amd.model import _DecoderFn
+    B, h, C, up, dtype = 2, 7, 128, 1, torch.float32
+    blk = _block(C)
+    for name in ("bn1", "bn2"):
+        old, bn = getattr(blk, name), torch.nn.BatchNorm2d(C, track_running_stats=False)
+        with torch.no_grad():
+            bn.weight.copy_(old.weight)
+            bn.bias.copy_(old.bias)
+        setattr(blk, name, bn)
+    assert blk.bn1.running_mean is None and blk.bn2.num_batches_tracked is None
+    g = torch.Generator().manual_seed(7)
+    feat = torch.randn(B, h, h, C, generator=g)
+    gy = torch.randn(B, h * up, h * up, C, generator=g)
+    params = [p.detach().double().requires_grad_() for p in _decoder_args(blk)]
+    fr = feat.double().requires_grad_()
+    yr = _ref(fr, *params, up, [None, None], [None, None], True)
+    (yr * gy.double()).sum().backward()
+    blk = blk.cuda().train(training)
+    fd = feat.cuda().requires_grad_()
+    y = _DecoderFn.apply(fd, *_decoder_args(blk), blk, up, dtype, training)
+    (y * gy.cuda()).sum().backward()
+    assert rel_l2(y.detach().cpu().numpy(), yr.detach().numpy()) < TOL[dtype]
+    _assert_decoder_grads(fd, blk, fr, params)
 
 
 def test_conv3x3_abi_matches_torch():
