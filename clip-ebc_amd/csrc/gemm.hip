@@ -1309,14 +1309,42 @@ namespace {
 //   (2-stage rings of 128-B K rows)   13: 128x96 S3 (conv weight gradients)
 //   15: 128x96 S3 + 4 loader waves   16: 128x96 S4 + 4 loader waves   (r03, tools/lab/gemm_lab.hip)
 // The L2 -> LDS fill rate per CU (~70 GB/s, MI355X_MICROARCH.md "gather into LDS") bounds a tile at
-// BM*BN/(BM+BN) flop per byte, so the default takes the 256-wide tiles and splits K where the
-// output has too few tiles to fill the 256 CUs.
-struct TileCfg { int id, bm, bn; };
-constexpr TileCfg CFGS[] = {{1, 128, 128}, {2, 128, 64}, {3, 256, 192}, {4, 192, 192}, {5, 128, 96}, {7, 256, 256},
-                            {13, 128, 96}, {15, 128, 96}, {16, 128, 96}, {17, 224, 192}};
+// BM*BN/(BM+BN) flop per byte, so the heuristics take the 256-wide tiles where the output has enough
+// of them to fill the 256 CUs (only the weight gradients split K instead: wgrad_plan).
+// Tile<ID> is the one place an id is tied to its kernel instance (tile, ring stages, wave grid, loader waves): the
+// planners read bm / bn / wgn from CFGS, built from it, and every launch takes its template arguments from it.
+template <int BM_, int BN_, int S_, int WGM_, int WGN_, int NLW_ = 0>
+struct TileShape { static constexpr int BM = BM_, BN = BN_, S = S_, WGM = WGM_, WGN = WGN_, NLW = NLW_; };
+template <int ID> struct Tile;
+template <> struct Tile<1> : TileShape<128, 128, 2, 2, 2> {};
+template <> struct Tile<2> : TileShape<128, 64, 2, 2, 2> {};
+template <> struct Tile<3> : TileShape<256, 192, 2, 4, 2> {};
+template <> struct Tile<4> : TileShape<192, 192, 2, 4, 2> {};
+template <> struct Tile<5> : TileShape<128, 96, 2, 2, 2> {};
+template <> struct Tile<7> : TileShape<256, 256, 2, 4, 2> {};
+template <> struct Tile<13> : TileShape<128, 96, 3, 2, 2> {};
+template <> struct Tile<15> : TileShape<128, 96, 3, 2, 2, 4> {};
+template <> struct Tile<16> : TileShape<128, 96, 4, 2, 2, 4> {};
+template <> struct Tile<17> : TileShape<224, 192, 2, 2, 4> {};
+
+struct TileCfg { int id, bm, bn, wgn; };
+template <int ID> constexpr TileCfg tile_cfg() { return {ID, Tile<ID>::BM, Tile<ID>::BN, Tile<ID>::WGN}; }
+constexpr TileCfg CFGS[] = {tile_cfg<1>(), tile_cfg<2>(), tile_cfg<3>(), tile_cfg<4>(), tile_cfg<5>(), tile_cfg<7>(),
+                            tile_cfg<13>(), tile_cfg<15>(), tile_cfg<16>(), tile_cfg<17>()};
 const TileCfg* find_cfg(int id) {
     for (const TileCfg& c : CFGS) if (c.id == id) return &c;
     return nullptr;
+}
+// f(Tile<ID>{}) for the id among IDs that cfg names; a site lists the ids it runs, and only those are instantiated
+template <int... IDs, class F>
+int with_tile(int cfg, F&& f) {
+    int rc = EBC_E_UNSUPPORTED;
+    (void)((cfg == IDs && (rc = f(Tile<IDs>{}), true)) || ...);
+    return rc;
+}
+template <class E, class TO, int EPI, int MODE, class T>
+int launch_tile(T, const GemmArgs& g, hipStream_t st) {
+    return launch_gemm<E, TO, EPI, T::BM, T::BN, T::S, T::WGM, T::WGN, 128, MODE, T::NLW>(g, st);
 }
 
 constexpr int NUM_CU = 256;
@@ -1368,21 +1396,20 @@ int pick_cfg(int M, int N, int K, bool wide) {
 // tiles spans one or two whole tile rows, so every XCD fetches all of B (c_fc: 46 MB fetched for 10.4 MB
 // of operands, PMC).  Grouping tile rows makes the XCD blocks squarer: the L2-miss bytes
 // A*ntn*GM/C + B*ntm/GM (C = tiles per XCD) are minimal at GM = sqrt(C * BN / BM).
-int group_rows(int M, int N, int bm, int bn, int splits) {
+int group_rows(int M, int N, int bm, int bn) {
     const long ntm = (M + bm - 1) / bm, ntn = N / bn;
-    if (ntn < 12 || splits > 1) return 0;
+    if (ntn < 12) return 0;
     const double C = (double)(ntm * ntn) / 8.0;
     const int gm = (int)(sqrt(C * bn / bm) + 0.5);
     return gm > 1 && gm < ntm ? gm : 0;
 }
-// the tile configuration a MODE 0 product runs
-int select_cfg(bool sixteen, int M, int N, int K) { return pick_cfg(M, N, K, sixteen); }
 
+// MODE 0 products: one split-free launch of the tile pick_cfg names
 template <class E, class TO, int EPI>
-int dispatch_tile(GemmArgs g, void* /*ws*/, size_t /*ws_bytes*/, hipStream_t st)
+int dispatch_tile(GemmArgs g, hipStream_t st)
 {
     constexpr bool SIXTEEN = E::BYTES == 2;
-    int cfg = select_cfg(SIXTEEN, g.M, g.N, g.K);
+    int cfg = pick_cfg(g.M, g.N, g.K, SIXTEEN);
     // EPI_LN_BWD stages BM rows x 32 partial pairs past the ring: the 256-row tiles the many-tile shapes pick (M >= ~24k
     // rows, e.g. 30 crops of 448) would need 180 KB of LDS, so those shapes run the 128x96 tile (several waves of
     // tiles there).  The tile of this product is free: the partials' count comes from the GELU' product's tiling.
@@ -1390,52 +1417,31 @@ int dispatch_tile(GemmArgs g, void* /*ws*/, size_t /*ws_bytes*/, hipStream_t st)
     const TileCfg* c = find_cfg(cfg);
     g.splits = 1;
     g.kslice = g.K;
-    g.group_m = group_rows(g.M, g.N, c->bm, c->bn, 1);
-    switch (cfg) {
-        case 1: return launch_gemm<E, TO, EPI, 128, 128, 2>(g, st);
-        case 2: return launch_gemm<E, TO, EPI, 128, 64, 2>(g, st);
-        case 4: return launch_gemm<E, TO, EPI, 192, 192, 2, 4, 2>(g, st);
-        case 5: return launch_gemm<E, TO, EPI, 128, 96, 2>(g, st);
-    }
-    if constexpr (EPI != EPI_LN_BWD) {
-        switch (cfg) {
-            case 3: return launch_gemm<E, TO, EPI, 256, 192, 2, 4, 2>(g, st);
-            case 7: return launch_gemm<E, TO, EPI, 256, 256, 2, 4, 2>(g, st);
-        }
-    }
-    if constexpr (SIXTEEN) {
-        switch (cfg) {
-            case 15: return launch_gemm<E, TO, EPI, 128, 96, 3, 2, 2, 128, 0, 4>(g, st);
-            case 16: return launch_gemm<E, TO, EPI, 128, 96, 4, 2, 2, 128, 0, 4>(g, st);
-        }
-    }
-    return EBC_E_UNSUPPORTED;
-}
-
-template <class E, int EPI>
-int dispatch_out(const GemmArgs& g, int out_f32, void* ws, size_t wsb, hipStream_t st)
-{
-    if (out_f32) return dispatch_tile<E, float, EPI>(g, ws, wsb, st);
-    return dispatch_tile<E, typename E::T, EPI>(g, ws, wsb, st);
+    g.group_m = group_rows(g.M, g.N, c->bm, c->bn);
+    const auto run = [&](auto t) { return launch_tile<E, TO, EPI, 0>(t, g, st); };
+    // (EPI_LN_BWD is 16-bit only: dispatch_epi)
+    if constexpr (!SIXTEEN) return with_tile<1, 2, 3, 4, 5, 7>(cfg, run);
+    else if constexpr (EPI == EPI_LN_BWD) return with_tile<1, 2, 4, 5, 15, 16>(cfg, run);
+    else return with_tile<1, 2, 3, 4, 5, 7, 15, 16>(cfg, run);
 }
 
 template <class E>
-int dispatch_epi(const GemmArgs& g, int epi, int out_f32, void* ws, size_t wsb, hipStream_t st)
+int dispatch_epi(const GemmArgs& g, int epi, int out_f32, hipStream_t st)
 {
+    using T = typename E::T;
     switch (epi) {
-        case EPI_STORE: return dispatch_out<E, EPI_STORE>(g, out_f32, ws, wsb, st);
-        case EPI_GELU: return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, typename E::T, EPI_GELU>(g, ws, wsb, st);
-        case EPI_RESID: return out_f32 ? dispatch_tile<E, float, EPI_RESID>(g, ws, wsb, st)
-                                       : dispatch_tile<E, typename E::T, EPI_RESID>(g, ws, wsb, st);
-        case EPI_GELU_BWD: return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, typename E::T, EPI_GELU_BWD>(g, ws, wsb, st);
+        case EPI_STORE: return out_f32 ? dispatch_tile<E, float, EPI_STORE>(g, st) : dispatch_tile<E, T, EPI_STORE>(g, st);
+        case EPI_GELU: return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, T, EPI_GELU>(g, st);
+        case EPI_RESID: return out_f32 ? dispatch_tile<E, float, EPI_RESID>(g, st) : dispatch_tile<E, T, EPI_RESID>(g, st);
+        case EPI_GELU_BWD: return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, T, EPI_GELU_BWD>(g, st);
         case EPI_LN:
-            if constexpr (E::BYTES == 2) return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, typename E::T, EPI_LN>(g, ws, wsb, st);
+            if constexpr (E::BYTES == 2) return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, T, EPI_LN>(g, st);
             return EBC_E_UNSUPPORTED;
         case EPI_LN_GELU:
-            if constexpr (E::BYTES == 2) return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, typename E::T, EPI_LN_GELU>(g, ws, wsb, st);
+            if constexpr (E::BYTES == 2) return out_f32 ? EBC_E_UNSUPPORTED : dispatch_tile<E, T, EPI_LN_GELU>(g, st);
             return EBC_E_UNSUPPORTED;
         case EPI_LN_BWD:
-            if constexpr (E::BYTES == 2) return out_f32 ? dispatch_tile<E, float, EPI_LN_BWD>(g, ws, wsb, st) : EBC_E_UNSUPPORTED;
+            if constexpr (E::BYTES == 2) return out_f32 ? dispatch_tile<E, float, EPI_LN_BWD>(g, st) : EBC_E_UNSUPPORTED;
             return EBC_E_UNSUPPORTED;
     }
     return EBC_E_ARG;
@@ -1446,24 +1452,10 @@ int dispatch_epi(const GemmArgs& g, int epi, int out_f32, void* ws, size_t wsb, 
 template <class E, class TO, int EPI, int MODE>
 int launch_conv_tile(const GemmArgs& g, int cfg, hipStream_t st)
 {
-    if (cfg == 2) return launch_gemm<E, TO, EPI, 128, 64, 2, 2, 2, 128, MODE>(g, st);
-    if constexpr (E::BYTES == 2) {
-#if EBC_CONV_LAB_W4   // lab only (0 in the library): 4-wave conv tiles, one 128x96 / 112x96 wave tile a SIMD
-        if (cfg == 3) return launch_gemm<E, TO, EPI, 256, 192, 2, 2, 2, 128, MODE>(g, st);
-#else
-        if (cfg == 3) return launch_gemm<E, TO, EPI, 256, 192, 2, 4, 2, 128, MODE>(g, st);
-#endif
-        if (cfg == 7) return launch_gemm<E, TO, EPI, 256, 256, 2, 4, 2, 128, MODE>(g, st);
-        if (cfg == 13) return launch_gemm<E, TO, EPI, 128, 96, 3, 2, 2, 128, MODE>(g, st);
-        if constexpr (MODE == 1) {
-#if EBC_CONV_LAB_W4
-            if (cfg == 17) return launch_gemm<E, TO, EPI, 224, 192, 2, 2, 2, 128, MODE>(g, st);
-#else
-            if (cfg == 17) return launch_gemm<E, TO, EPI, 224, 192, 2, 2, 4, 128, MODE>(g, st);
-#endif
-        }
-    }
-    return EBC_E_UNSUPPORTED;
+    const auto run = [&](auto t) { return launch_tile<E, TO, EPI, MODE>(t, g, st); };
+    if constexpr (E::BYTES != 2) return with_tile<2>(cfg, run);
+    else if constexpr (MODE == 1) return with_tile<2, 3, 7, 13, 17>(cfg, run);
+    else return with_tile<2, 3, 7, 13>(cfg, run);
 }
 
 // Weight-gradient products (MODE 2 conv dW, and ebc_gemm_wgrad's 1x1 dW): small outputs, long K (pixels).
@@ -1594,27 +1586,29 @@ size_t sk_ws_bytes(int cfg, const SkPlan& p) {
 }
 // conv workspace: [arrival counters][EPI_STATS per-tile-row partials (BM >= 128)][stream-K partials]
 size_t conv_stats_bytes(int M, int N) { return (((size_t)((M + 127) / 128) * 2 * N * 4 + 255) / 256) * 256; }
-int conv_splits(int cfg, int mode, int M, int N, int nk)
+// the (mode, epilogue) pairs the convolutions run
+template <class E>
+int launch_conv(const GemmArgs& g, int mode, int epi, int cfg, hipStream_t st)
 {
-    if (mode != 2) return 1;
-    const TileCfg* c = find_cfg(cfg);
-    const long tiles = ntiles(M, N, c->bm, c->bn);
-    int s = 1;
-    while (tiles * (s + 1) <= NUM_CU * 6 / 5 && nk % (s + 1) == 0 && nk / (s + 1) >= 16) ++s;
-    return s;
+    using T = typename E::T;
+    if (mode == 1 && epi == EPI_STORE) return launch_conv_tile<E, T, EPI_STORE, 1>(g, cfg, st);
+    if (mode == 1 && epi == EPI_STATS) return launch_conv_tile<E, T, EPI_STATS, 1>(g, cfg, st);
+    if (mode == 1 && epi == EPI_ADD_RELU_GRAD) return launch_conv_tile<E, T, EPI_ADD_RELU_GRAD, 1>(g, cfg, st);
+    if (mode == 2 && epi == EPI_STORE) return launch_conv_tile<E, float, EPI_STORE, 2>(g, cfg, st);
+    return EBC_E_UNSUPPORTED;
 }
 
 template <class E>
 int dispatch_conv(GemmArgs g, int mode, int epi, void* ws, size_t wsb, hipStream_t st)
 {
     constexpr bool SIXTEEN = E::BYTES == 2;
-    const bool planned = mode == 2;
-    const WPlan wp = planned ? wgrad_plan(SIXTEEN, true, g.M, g.N, g.K) : WPlan{0, 1, false};
-    const int cfg = planned ? wp.cfg : conv_cfg(SIXTEEN, mode, g.M, g.N);
+    // only the weight gradients (mode 2) split K
+    const WPlan wp = mode == 2 ? wgrad_plan(SIXTEEN, true, g.M, g.N, g.K) : WPlan{conv_cfg(SIXTEEN, mode, g.M, g.N), 1, false};
+    const int cfg = wp.cfg;
     const int BK = 128 / E::BYTES;
     const TileCfg* c = find_cfg(cfg);
     if (g.N % c->bn || g.K % BK) return EBC_E_UNSUPPORTED;
-    if (planned && wp.partials) {
+    if (wp.partials) {
         if (!ws || wsb < wplan_ws(wp, g.M, g.N)) return EBC_E_ARG;
         g.part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + GEMM_CNT_BYTES);
         g.cnt = nullptr;
@@ -1623,8 +1617,7 @@ int dispatch_conv(GemmArgs g, int mode, int epi, void* ws, size_t wsb, hipStream
         EBC_TRY((launch_conv_tile<E, float, EPI_STORE, 2>(g, cfg, st)));
         return splitk_reduce(g.part, reinterpret_cast<float*>(g.C), (long)g.M * g.N, wp.splits, st);
     }
-    int splits = planned ? wp.splits : conv_splits(cfg, mode, g.M, g.N, g.K / BK);
-    using T = typename E::T;
+    int splits = wp.splits;
     if (SIXTEEN) {
         const SkPlan sk = sk_plan(mode, cfg, g.M, g.N, g.K, BK, ntiles(g.M, g.N, c->bm, c->bn) * splits);
         const size_t off = GEMM_CNT_BYTES + (mode == 1 ? conv_stats_bytes(g.M, g.N) : 0);
@@ -1634,11 +1627,7 @@ int dispatch_conv(GemmArgs g, int mode, int epi, void* ws, size_t wsb, hipStream
             if (sk.dp) {
                 GemmArgs d = g;
                 d.ntile = sk.dp;
-                if (mode == 1 && epi == EPI_STORE) EBC_TRY((launch_conv_tile<E, T, EPI_STORE, 1>(d, cfg, st)));
-                else if (mode == 1 && epi == EPI_STATS) EBC_TRY((launch_conv_tile<E, T, EPI_STATS, 1>(d, cfg, st)));
-                else if (mode == 1 && epi == EPI_ADD_RELU_GRAD) EBC_TRY((launch_conv_tile<E, T, EPI_ADD_RELU_GRAD, 1>(d, cfg, st)));
-                else if (mode == 2 && epi == EPI_STORE) EBC_TRY((launch_conv_tile<E, float, EPI_STORE, 2>(d, cfg, st)));
-                else return EBC_E_UNSUPPORTED;
+                EBC_TRY(launch_conv<E>(d, mode, epi, cfg, st));
                 g.tile0 = sk.dp;
             }
             g.sk_total = sk.total;
@@ -1647,11 +1636,7 @@ int dispatch_conv(GemmArgs g, int mode, int epi, void* ws, size_t wsb, hipStream
             g.sk_share = sk.share;
             g.cnt = reinterpret_cast<int*>(ws);
             g.part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off);
-            if (mode == 1 && epi == EPI_STORE) return launch_conv_tile<E, T, EPI_STORE, 1>(g, cfg, st);
-            if (mode == 1 && epi == EPI_STATS) return launch_conv_tile<E, T, EPI_STATS, 1>(g, cfg, st);
-            if (mode == 1 && epi == EPI_ADD_RELU_GRAD) return launch_conv_tile<E, T, EPI_ADD_RELU_GRAD, 1>(g, cfg, st);
-            if (mode == 2 && epi == EPI_STORE) return launch_conv_tile<E, float, EPI_STORE, 2>(g, cfg, st);
-            return EBC_E_UNSUPPORTED;
+            return launch_conv<E>(g, mode, epi, cfg, st);
         }
     }
     if (splits > 1) {
@@ -1666,11 +1651,7 @@ int dispatch_conv(GemmArgs g, int mode, int epi, void* ws, size_t wsb, hipStream
     }
     g.splits = splits;
     g.kslice = g.K / splits;
-    if (mode == 1 && epi == EPI_STORE) return launch_conv_tile<E, T, EPI_STORE, 1>(g, cfg, st);
-    if (mode == 1 && epi == EPI_STATS) return launch_conv_tile<E, T, EPI_STATS, 1>(g, cfg, st);
-    if (mode == 1 && epi == EPI_ADD_RELU_GRAD) return launch_conv_tile<E, T, EPI_ADD_RELU_GRAD, 1>(g, cfg, st);
-    if (mode == 2 && epi == EPI_STORE) return launch_conv_tile<E, float, EPI_STORE, 2>(g, cfg, st);
-    return EBC_E_UNSUPPORTED;
+    return launch_conv<E>(g, mode, epi, cfg, st);
 }
 
 }  // namespace
@@ -1697,11 +1678,6 @@ size_t conv_gemm_workspace_bytes(int dtype, int mode, int M, int N, int K)
         }
         return std::max({need, wplan_ws(wp, M, N), skb});
     }
-    const int cfg = conv_cfg(sixteen, mode, M, N);
-    const TileCfg* c = find_cfg(cfg);
-    const int bk = !sixteen ? 32 : 64;
-    const int s = conv_splits(cfg, mode, M, N, K / bk);
-    if (s > 1) need = std::max(need, GEMM_CNT_BYTES + (size_t)s * ntiles(M, N, c->bm, c->bn) * c->bm * c->bn * 4);
     return need;
 }
 
@@ -1735,14 +1711,9 @@ int conv_gemm(int dtype, int mode, int epi, const void* A, const void* B, void* 
     return EBC_E_ARG;
 }
 
-size_t gemm_workspace_bytes(int, int, int, int)
-{
-    return 0;             // the MODE 0 products never split K (see pick_cfg), so they take no workspace
-}
-
+// the MODE 0 products never split K (see pick_cfg), so they take no workspace
 int gemm_nt(int dtype, int epi, int out_f32, const void* A, const void* B, void* C, const float* bias,
-            const float* resid, void* aux, int M, int N, int K, hipStream_t st, void* ws, size_t ws_bytes,
-            int a_rpg, int a_gstride, int a_goff)
+            const float* resid, void* aux, int M, int N, int K, hipStream_t st, int a_rpg, int a_gstride, int a_goff)
 {
     const int bk = dtype == EBC_F32 ? 32 : 64;
     if (M <= 0 || N <= 0 || K <= 0 || K % bk != 0 || N % 64 != 0 || !A || !B || !C) return EBC_E_ARG;
@@ -1751,9 +1722,9 @@ int gemm_nt(int dtype, int epi, int out_f32, const void* A, const void* B, void*
     GemmArgs g{A, B, C, bias, resid, aux, M, N, K};
     g.a_rpg = a_rpg; g.a_gstride = a_gstride; g.a_goff = a_goff;
     switch (dtype) {
-        case EBC_F32: return dispatch_epi<EF32>(g, epi, 0, nullptr, 0, st);   // element type is already f32
-        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, ws, ws_bytes, st);
-        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, ws, ws_bytes, st);
+        case EBC_F32: return dispatch_epi<EF32>(g, epi, 0, st);   // element type is already f32
+        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, st);
+        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, st);
     }
     return EBC_E_ARG;
 }
@@ -1765,19 +1736,18 @@ bool gemm_ln_bwd_fold_pays(int dtype, int M, int N, int K)
     // tile the many-tile shapes take (cfg 5: two workgroups a CU at 57 KB) it halves the workgroups a CU holds: 32
     // crops (M = 7328) ran the folded c_fc dX at 86 us against 45 + 16 us for the product + LayerNorm launch pair, bench
     // 3923 vs 4082 crops/s (r06h, profiles/r06h_ln_bwd_fold_32crops.txt).  The fold is taken where it pays.
-    const int cfg = select_cfg(dtype != EBC_F32, M, N, K);
+    const int cfg = pick_cfg(M, N, K, dtype != EBC_F32);
     return cfg == 15 || cfg == 16;
 }
 
 int gemm_rowstat_parts(int dtype, int M, int N, int K)
 {
-    const TileCfg* c = find_cfg(select_cfg(dtype != EBC_F32, M, N, K));
-    return N / c->bn * 2;                       // every MODE 0 tile configuration has 2 wave columns
+    const TileCfg* c = find_cfg(pick_cfg(M, N, K, dtype != EBC_F32));
+    return N / c->bn * c->wgn;                  // one partial pair per tile column and wave column
 }
 
 int gemm_nt_ln(int dtype, int epi, int out_f32, const void* A, const void* B, void* C, const float* bias,
-               const float* resid, void* aux, int M, int N, int K, hipStream_t st, void* ws, size_t ws_bytes,
-               const GemmLn& ln)
+               const float* resid, void* aux, int M, int N, int K, hipStream_t st, const GemmLn& ln)
 {
     const int bk = dtype == EBC_F32 ? 32 : 64;
     if (dtype == EBC_F32 || M <= 0 || N <= 0 || K <= 0 || K % bk != 0 || N % 64 != 0 || !A || !B || !C) return EBC_E_ARG;
@@ -1817,8 +1787,8 @@ int gemm_nt_ln(int dtype, int epi, int out_f32, const void* A, const void* B, vo
         return EBC_E_ARG;
     }
     switch (dtype) {
-        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, ws, ws_bytes, st);
-        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, ws, ws_bytes, st);
+        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, st);
+        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, st);
     }
     return EBC_E_ARG;
 }
@@ -1844,17 +1814,11 @@ int wgrad_launch(GemmArgs g, void* ws, size_t wsb, hipStream_t st) {
     g.splits = s;
     g.kslice = g.K / s;
     g.group_m = 0;
-    int rc = EBC_E_UNSUPPORTED;
-    if constexpr (SIXTEEN) {
-        switch (wp.cfg) {
-            case 7: rc = launch_gemm<E, float, EPI_STORE, 256, 256, 2, 4, 2>(g, st); break;
-            case 3: rc = launch_gemm<E, float, EPI_STORE, 256, 192, 2, 4, 2>(g, st); break;
-            case 1: rc = launch_gemm<E, float, EPI_STORE, 128, 128, 2>(g, st); break;
-            default: rc = launch_gemm<E, float, EPI_STORE, 128, 64, 2>(g, st); break;
-        }
-    } else {
-        rc = launch_gemm<E, float, EPI_STORE, 128, 64, 2>(g, st);
-    }
+    // wgrad_plan's candidates (cand16_gemm / cand32)
+    const auto run = [&](auto t) { return launch_tile<E, float, EPI_STORE, 0>(t, g, st); };
+    int rc;
+    if constexpr (SIXTEEN) rc = with_tile<7, 3, 1, 2>(wp.cfg, run);
+    else rc = with_tile<2>(wp.cfg, run);
     if (rc || !(s > 1 && wp.partials)) return rc;
     return splitk_reduce(g.part, reinterpret_cast<float*>(g.C), (long)g.M * g.N, s, st);
 }
@@ -1931,29 +1895,13 @@ extern "C" int ebc_gemm(int dtype, int epilogue, int out_f32, const void* A, con
                         const float* bias, const float* resid, void* aux, int M, int N, int K,
                         ebc_stream_t stream)
 {
-    return ebc::gemm_nt(dtype, epilogue, out_f32, A, B, C, bias, resid, aux, M, N, K, (hipStream_t)stream, nullptr, 0);
-}
-
-extern "C" size_t ebc_gemm_workspace_bytes(int dtype, int M, int N, int K)
-{
-    return ebc::gemm_workspace_bytes(dtype, M, N, K);
-}
-
-extern "C" int ebc_gemm_ws(int dtype, int epilogue, int out_f32, const void* A, const void* B, void* C,
-                           const float* bias, const float* resid, void* aux, int M, int N, int K,
-                           void* workspace, size_t workspace_bytes, ebc_stream_t stream)
-{
-    // workspace contract (include/ebc_hip.h): zero-filled before its first use, then owned by the
-    // caller's stream; the kernels leave its counter block zero again after every call
-    return ebc::gemm_nt(dtype, epilogue, out_f32, A, B, C, bias, resid, aux, M, N, K, (hipStream_t)stream,
-                        workspace, workspace_bytes);
+    return ebc::gemm_nt(dtype, epilogue, out_f32, A, B, C, bias, resid, aux, M, N, K, (hipStream_t)stream);
 }
 
 extern "C" int ebc_gemm_tile_config(int dtype, int M, int N, int K, int* out)
 {
     if (M <= 0 || N <= 0 || K <= 0 || (dtype != EBC_F32 && dtype != EBC_F16 && dtype != EBC_BF16)) return EBC_E_ARG;
-    const bool sixteen = dtype != EBC_F32;
-    const int cfg = select_cfg(sixteen, M, N, K);
+    const int cfg = pick_cfg(M, N, K, dtype != EBC_F32);
     const TileCfg* c = find_cfg(cfg);
     if (out) {
         out[0] = c->bm;
@@ -1968,7 +1916,7 @@ extern "C" int ebc_conv_tile_config(int dtype, int mode, int M, int N, int K, in
     if (M <= 0 || N <= 0 || K <= 0 || (mode != 1 && mode != 2)) return EBC_E_ARG;
     const bool sixteen = dtype != EBC_F32;
     const int bk = !sixteen ? 32 : 64;
-    int cfg, splits;
+    int cfg, splits = 1;
     if (mode == 2) {
         const WPlan wp = wgrad_plan(sixteen, true, M, N, K);
         cfg = wp.cfg;
@@ -1976,7 +1924,6 @@ extern "C" int ebc_conv_tile_config(int dtype, int mode, int M, int N, int K, in
         if (wp.partials) splits = -splits;           // never stream-K: reported as split-K
     } else {
         cfg = conv_cfg(sixteen, mode, M, N);
-        splits = conv_splits(cfg, mode, M, N, K / bk);
     }
     const TileCfg* c = find_cfg(cfg);
     if (splits < 0) {

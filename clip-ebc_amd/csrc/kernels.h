@@ -19,9 +19,12 @@ bool touch_enabled();
 bool probe_on();
 int probe_start(int kind, int epi, int bm, int bn, int mode, int m, int n, int k, hipStream_t st);
 void probe_stop(int idx, hipStream_t st);
+// C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue (include/ebc_hip.h ebc_gemm).  a_rpg > 0 (EPI_STORE only) maps the A
+// rows: output row r reads A row (r / a_rpg) * a_gstride + a_goff + r % a_rpg, i.e. a_rpg rows from offset a_goff of
+// every group of a_gstride rows (layer 0's prompt rows of each crop)
 int gemm_nt(int dtype, int epi, int out_f32, const void* A, const void* B, void* C, const float* bias,
-            const float* resid, void* aux, int M, int N, int K, hipStream_t st, void* ws = nullptr,
-            size_t ws_bytes = 0, int a_rpg = 0, int a_gstride = 0, int a_goff = 0);
+            const float* resid, void* aux, int M, int N, int K, hipStream_t st, int a_rpg = 0, int a_gstride = 0,
+            int a_goff = 0);
 // LayerNorm folded into the encoder GEMMs (gemm.hip GemmArgs, vit.hip; 16-bit): a RESID product that also writes a
 // compute-dtype copy of its rows (xh) and per-row partial sums / sums of squares (rpart [M][parts][2],
 // parts = gemm_rowstat_parts), and GEMM_EPI_LN / GEMM_EPI_LN_GELU products normalising their A rows from them
@@ -52,13 +55,10 @@ constexpr int GEMM_EPI_LN = 6, GEMM_EPI_LN_GELU = 7, GEMM_EPI_LN_BWD = 8;
 constexpr int GEMM_LN_PMAX = 16;   // most row partials an EPI_LN product reads (gemm_rowstat_parts of its producer)
 constexpr int GEMM_LN_PMAX_B = 32; // ... and an EPI_LN_BWD product (the GELU' product's: 3072 / 192 x 2)
 int gemm_nt_ln(int dtype, int epi, int out_f32, const void* A, const void* B, void* C, const float* bias,
-               const float* resid, void* aux, int M, int N, int K, hipStream_t st, void* ws, size_t ws_bytes,
-               const GemmLn& ln);
+               const float* resid, void* aux, int M, int N, int K, hipStream_t st, const GemmLn& ln);
 int gemm_rowstat_parts(int dtype, int M, int N, int K);
 // whether the c_fc dX product (M x N = 768 x K = 3072) runs the LayerNorm-backward epilogue without losing occupancy
 bool gemm_ln_bwd_fold_pays(int dtype, int M, int N, int K);
-// split-K workspace the heuristic wants for this shape (0: no split); zero-filled counter block first
-size_t gemm_workspace_bytes(int dtype, int M, int N, int K);
 // implicit-GEMM 3x3 convolution geometry (gemm.hip MODE 1 / MODE 2)
 struct ConvGeom {
     int H, W, C;      // output image (stride 1, pad 1), channels per tap

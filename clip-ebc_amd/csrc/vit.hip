@@ -54,8 +54,6 @@ struct Layout {
     int parts_out, parts_proj;      //   written by the out-proj / c_proj residual products (gemm_rowstat_parts)
     float* bpart;                   // LayerNorm-backward folding: [M][parts_gelu][2] partials of the GELU' products
     int parts_gelu;
-    void* gws;                      // split-K GEMM workspace (leading counter block zeroed per call)
-    size_t gws_bytes;
     size_t bytes;
 };
 
@@ -122,13 +120,6 @@ Layout carve(void* ws, int B, int L, int G, int KP, int layers, int dtype, int t
         lay.parts_out = lay.parts_proj = 0;
         lay.rpart = nullptr;
     }
-    // the largest split-K workspace any of the encoder GEMMs asks for
-    size_t g = ebc::gemm_workspace_bytes(dtype, B * G, WIDTH, KP);             // patch embedding
-    const int Mi = (int)M;
-    const int shapes[][2] = {{QKVW, WIDTH}, {WIDTH, WIDTH}, {MLP, WIDTH}, {WIDTH, MLP}, {WIDTH, QKVW}};
-    for (const auto& sh : shapes) g = std::max(g, ebc::gemm_workspace_bytes(dtype, Mi, sh[0], sh[1]));
-    lay.gws_bytes = g;
-    lay.gws = g ? c.take<void>(g) : nullptr;
     lay.bytes = c.off;
     return lay;
 }
@@ -169,11 +160,9 @@ extern "C" int ebc_vit_forward(const EbcVitWeights* w, const float* image, int B
     Layout lay = carve(ws, B, L, G, KP, layers, dtype, training);
     if (lay.bytes > ws_bytes) return EBC_E_ARG;
     if (NV > 0 && (!vpt || !vpt[0])) return EBC_E_ARG;
-    if (lay.gws && hipMemsetAsync(lay.gws, 0, std::min<size_t>(lay.gws_bytes, 16 * 1024), st) != hipSuccess)
-        return EBC_E_LAUNCH;
     auto gemm = [&](int epi, int out_f32, const void* A, const void* Bm, void* C, const float* bias, const float* resid,
                     void* aux, int m, int n, int k) {
-        return ebc::gemm_nt(dtype, epi, out_f32, A, Bm, C, bias, resid, aux, m, n, k, st, lay.gws, lay.gws_bytes);
+        return ebc::gemm_nt(dtype, epi, out_f32, A, Bm, C, bias, resid, aux, m, n, k, st);
     };
 
     // patch embedding: im2col + GEMM with conv1 weight [768, 3*patch*patch] (image_encoder.py:141)
@@ -223,11 +212,11 @@ extern "C" int ebc_vit_forward(const EbcVitWeights* w, const float* image, int B
         float* lse = s.lse + (size_t)b0 * HEADS * L;
         auto gemm = [&](int epi, int out_f32, const void* Am, const void* Bm, void* C, const float* bias,
                         const float* resid, void* aux, int n, int k) {
-            return ebc::gemm_nt(dtype, epi, out_f32, Am, Bm, C, bias, resid, aux, m, n, k, sx, lay.gws, lay.gws_bytes);
+            return ebc::gemm_nt(dtype, epi, out_f32, Am, Bm, C, bias, resid, aux, m, n, k, sx);
         };
         auto gemm_ln = [&](int epi, int out_f32, const void* Am, const void* Bm, void* C, const float* bias,
                            const float* resid, void* aux, int n, int k, const ebc::GemmLn& ln) {
-            return ebc::gemm_nt_ln(dtype, epi, out_f32, Am, Bm, C, bias, resid, aux, m, n, k, sx, lay.gws, lay.gws_bytes, ln);
+            return ebc::gemm_nt_ln(dtype, epi, out_f32, Am, Bm, C, bias, resid, aux, m, n, k, sx, ln);
         };
         // x = x + out_proj(attn(ln_1(x))); deep VPT: the prompt rows come from vpt_l (written into X)
         const bool vrows = l > 0 && NV > 0 && vpt[l];
@@ -301,10 +290,8 @@ extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int
     // ln_post backward into the patch rows of dX_L; CLS / prompt rows get zero gradient
     float* dX = lay.dXa;
     float* dXo = lay.dXb;
-    if (lay.gws && hipMemsetAsync(lay.gws, 0, std::min<size_t>(lay.gws_bytes, 16 * 1024), st) != hipSuccess)
-        return EBC_E_LAUNCH;
     auto gemm = [&](int epi, const void* A, const void* Bm, void* C, void* aux, int m, int n, int k) {
-        return ebc::gemm_nt(dtype, epi, 0, A, Bm, C, nullptr, nullptr, aux, m, n, k, st, lay.gws, lay.gws_bytes);
+        return ebc::gemm_nt(dtype, epi, 0, A, Bm, C, nullptr, nullptr, aux, m, n, k, st);
     };
     // ln_2's backward folded into the c_fc dX product (16-bit, every layer carrying (W_fc')^T): the GELU' product also
     // writes, per row, the partial sums sum_k dA_k s_k and sum_k dA_k (A_k - c_k) over its columns (s = W_fc'.1, c = the
@@ -346,11 +333,11 @@ extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int
             ebc::GemmLn gb;
             gb.bpart = lay.bpart; gb.lnb_s = p.s_fc_ln; gb.lnb_c = p.b_fc_ln;
             EBC_TRY(ebc::gemm_nt_ln(dtype, EBC_EPI_GELU_BWD, 0, lay.dXt, p.wt_proj, lay.dA, nullptr, nullptr, s.A, M, MLP,
-                                    WIDTH, st, lay.gws, lay.gws_bytes, gb));
+                                    WIDTH, st, gb));
             ebc::GemmLn lb;
             lb.xh = lay.dXt; lb.lnx = s.X1; lb.lnp = lay.bpart; lb.lnparts = lay.parts_gelu; lb.mean = s.m2; lb.rstd = s.r2;
             EBC_TRY(ebc::gemm_nt_ln(dtype, ebc::GEMM_EPI_LN_BWD, 1, lay.dA, p.wt_fc_ln, dXo, nullptr, dX, nullptr, M, WIDTH,
-                                    MLP, st, lay.gws, lay.gws_bytes, lb));
+                                    MLP, st, lb));
         } else {
             EBC_TRY(gemm(EBC_EPI_GELU_BWD, lay.dXt, p.wt_proj, lay.dA, s.A, M, MLP, WIDTH));
             EBC_TRY(gemm(EBC_EPI_STORE, lay.dA, p.wt_fc, lay.dH, nullptr, M, WIDTH, MLP));
@@ -366,7 +353,7 @@ extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int
             // rows (same values as the full backward's rows: every kept element is summed in the same order)
             EBC_TRY(ebc::attention_bwd(dtype, s.QKV, lay.dO, s.O, s.lse, lay.delta, lay.dQKV, B, L, HEADS, st, 1 + NV, &tl));
             EBC_TRY(ebc::gemm_nt(dtype, EBC_EPI_STORE, 0, lay.dQKV, p.wt_qkv, lay.dH, nullptr, nullptr, nullptr, B * NV,
-                                 WIDTH, QKVW, st, lay.gws, lay.gws_bytes, NV, L, 1));
+                                 WIDTH, QKVW, st, NV, L, 1));
             float* rows = per_batch ? dvpt[0] : lay.vpt_rows;
             EBC_TRY(ebc::layernorm_bwd_rows(dtype, lay.dH, lay.X[0], NV, L, 1, s.m1, s.r1, p.ln1_g, dX, rows, B * NV,
                                             WIDTH, st));

@@ -113,22 +113,16 @@ int ebc_sinkhorn(const float* a, const float* b, const float* C, int na, int nb,
 enum { EBC_EPI_STORE = 0, EBC_EPI_GELU = 1, EBC_EPI_RESID = 2, EBC_EPI_GELU_BWD = 3 };
 int ebc_gemm(int dtype, int epilogue, int out_f32, const void* A, const void* B, void* C,
              const float* bias, const float* resid, void* aux, int M, int N, int K, ebc_stream_t stream);
-/* The tile configuration ebc_gemm / ebc_gemm_ws dispatch for this shape (host-only, no device work):
- * returns the configuration id (> 0; EBC_GEMM_CFG overrides are honoured as in the launch) and writes
- * out[3] = {tile rows, tile columns, split-K factor}.  Lets tests pin which kernel instance a shape runs. */
+/* The tile configuration ebc_gemm dispatches for this shape (host-only, no device work): returns the
+ * configuration id (> 0; a function of dtype and shape alone) and writes out[3] = {tile rows, tile columns, 1}
+ * (these products never split K).  Lets tests pin which kernel instance a shape runs. */
 int ebc_gemm_tile_config(int dtype, int M, int N, int K, int* out);
-/* Same, allowed to split K over workgroups (16-bit dtypes) when the output has too few 256-wide
- * tiles to fill the GPU.  `workspace` (>= ebc_gemm_workspace_bytes; 0 = no split for this shape)
- * must be zero-filled before its first use and is then owned by the stream: every call leaves
- * its leading counter block zero again, the rest is scratch. */
-size_t ebc_gemm_workspace_bytes(int dtype, int M, int N, int K);
-int ebc_gemm_ws(int dtype, int epilogue, int out_f32, const void* A, const void* B, void* C,
-                const float* bias, const float* resid, void* aux, int M, int N, int K,
-                void* workspace, size_t workspace_bytes, ebc_stream_t stream);
 /* Weight-gradient GEMM for a long reduction (K = pixels), f32 output:  C[M,N] = A[M,K] . B[N,K]^T
  * with A, B in `dtype` (K-contiguous: the transposed activations / output gradients).  Replaces the
  * projection's dW = dZ^T Y of models/clip/model.py:91-95 (nn.Conv2d 1x1 backward).  Splits K over
- * workgroups (deterministic last-arriver sum); `workspace` as for ebc_gemm_ws. */
+ * workgroups (deterministic last-arriver sum).  `workspace` (>= ebc_gemm_wgrad_workspace_bytes; 0 = no
+ * split for this shape) must be zero-filled before its first use and is then owned by the stream: every
+ * call leaves its leading 16 KiB counter block zero again, the rest is scratch. */
 size_t ebc_gemm_wgrad_workspace_bytes(int dtype, int M, int N, int K);
 int ebc_gemm_wgrad(int dtype, const void* A, const void* B, float* C, int M, int N, int K,
                    void* workspace, size_t workspace_bytes, ebc_stream_t stream);

@@ -1,5 +1,4 @@
-"""Decoder conv GEMMs alone (fwd+stats, dgrad, wgrad) at the bench shape, HIP-event timed.
-EBC_CONV_CFG=<cfg> forces the tile config (gemm.hip)."""
+"""Decoder conv GEMMs alone (fwd+stats, dgrad, wgrad) at the bench shape, HIP-event timed."""
 import ctypes
 import os
 import sys
@@ -48,8 +47,12 @@ def main():
                                           ws.numel(), B, H, W, C, C, st))
     t3 = timeit(lambda: L.ebc_conv3x3_wgrad(dt, _lib.ptr(dzT), _lib.ptr(xT3), _lib.ptr(dw), _lib.ptr(ws), ws.numel(),
                                             B, H, W, C, C, st))
-    cfg = os.environ.get("EBC_CONV_CFG", "auto") + " tail=" + os.environ.get("EBC_CONV_TAIL", "1")
-    print(f"B={B} H={H} C={C} cfg {cfg:>4}: fwd+stats {t1*1e6:7.1f} us {f/t1/1e12:6.0f} TF/s | fwd {t2*1e6:7.1f} us {f/t2/1e12:6.0f} TF/s"
+    tile = (ctypes.c_int * 3)()
+    cfg = []      # ebc_conv_tile_config: id tile-rows x tile-columns / splits (< 0: a stream-K grid) of the forward and dW
+    for mode, (m, n, k) in ((1, (B * H * W, C, 9 * C)), (2, (C, 9 * C, geo[3]))):
+        cfg.append(f"{L.ebc_conv_tile_config(dt, mode, m, n, k, tile)} {tile[0]}x{tile[1]}/{tile[2]}")
+    cfg = "fwd " + cfg[0] + ", wgrad " + cfg[1]
+    print(f"B={B} H={H} C={C} cfg {cfg}: fwd+stats {t1*1e6:7.1f} us {f/t1/1e12:6.0f} TF/s | fwd {t2*1e6:7.1f} us {f/t2/1e12:6.0f} TF/s"
           f" | wgrad {t3*1e6:7.1f} us {f/t3/1e12:6.0f} TF/s (algorithmic)")
 
 

@@ -180,7 +180,7 @@ int main(int argc, char** argv)
                     inst += t;
                 }
                 inst /= reps;
-                printf("%s r%d %-18s %-18s alone %7.2f us (%6.1f TF/s)   after c_fc %7.2f us (%6.1f TF/s)\n", EBC_STORE_NT ? "nt" : "plain", r, sh.name,
+                printf("r%d %-18s %-18s alone %7.2f us (%6.1f TF/s)   after c_fc %7.2f us (%6.1f TF/s)\n", r, sh.name,
                        v.name.c_str(), alone * 1e3, tf / (alone * 1e-3), inst * 1e3, tf / (inst * 1e-3));
             }
         }
@@ -250,7 +250,7 @@ int main(int argc, char** argv)
                         CK(hipEventElapsedTime(&t2, ev[2 * l + 1], e2));
                         if (it > 0) { fc += t1; tot += t2; }
                     }
-                printf("%s r%d mlp-seq c_proj %-16s %7.2f us   (c_fc %7.2f us)\n", EBC_STORE_NT ? "nt" : "plain", r, v.name,
+                printf("r%d mlp-seq c_proj %-16s %7.2f us   (c_fc %7.2f us)\n", r, v.name,
                        tot / (2 * NL) * 1e3, fc / (2 * NL) * 1e3);
             }
     }
@@ -262,7 +262,7 @@ int main(int argc, char** argv)
         CK(hipEventSynchronize(e1));
         float t = 0;
         CK(hipEventElapsedTime(&t, e0, e1));
-        printf("%s r%d c_fc+gelu 256x192 alone %7.2f us\n", EBC_STORE_NT ? "nt" : "plain", r, t / reps * 1e3);
+        printf("r%d c_fc+gelu 256x192 alone %7.2f us\n", r, t / reps * 1e3);
     }
     return 0;
 }
