@@ -1379,6 +1379,8 @@ int attention_bwd(int dtype, const void* qkv, const void* dout, const void* out,
         }
         return EBC_E_ARG;
     }
+    // the f32 dQ kernel publishes delta for the dK/dV kernel; the 16-bit one-workgroup kernel keeps it in LDS
+    if (dtype == EBC_F32 && !delta) return EBC_E_ARG;
     switch (dtype) {
         case EBC_F32: return attn_bwd_t<EF32>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows, nullptr);
         case EBC_F16: return attn_bwd_t<EF16>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows, touch);

@@ -379,10 +379,18 @@ extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int
 }
 
 // ---------------------------------------------------------------------------- kernel C-ABI
+// The single-kernel entry points validate on the host, before any device work (EBC_E_ARG); the in-library callers above
+// go to the ebc:: launchers directly.
+static bool ln_map_ok(int rpg, int gstride, int goff)
+{
+    return rpg <= 0 || (goff >= 0 && (long)goff + rpg <= (long)gstride);
+}
 extern "C" int ebc_layernorm_fwd(int dtype, const float* x, int rows_per_group, int group_stride, int group_offset,
                                  const float* gamma, const float* beta, void* out, float* out_f32, float* mean,
                                  float* rstd, int M, int D, ebc_stream_t stream)
 {
+    if (!x || !gamma || !beta || (!out && !out_f32) || (mean && !rstd)) return EBC_E_ARG;
+    if (!ln_map_ok(rows_per_group, group_stride, group_offset)) return EBC_E_ARG;
     return ebc::layernorm_fwd(dtype, x, rows_per_group, group_stride, group_offset, gamma, beta, out, out_f32, mean,
                               rstd, M, D, (hipStream_t)stream);
 }
@@ -391,21 +399,27 @@ extern "C" int ebc_layernorm_bwd(int dtype, int dy_f32, const void* dy, const fl
                                  const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, int D,
                                  ebc_stream_t stream)
 {
+    if (!dy || !x || !mean || !rstd || !gamma || !dx_out) return EBC_E_ARG;
+    if (!ln_map_ok(rows_per_group, group_stride, group_offset)) return EBC_E_ARG;
     return ebc::layernorm_bwd(dtype, dy_f32, dy, x, rows_per_group, group_stride, group_offset, mean, rstd, gamma,
                               dx_in, dx_out, dx_out_t, M, D, (hipStream_t)stream);
 }
 extern "C" int ebc_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream)
 {
+    if (!qkv || !out) return EBC_E_ARG;
     return ebc::attention_fwd(dtype, qkv, out, lse, B, L, H, (hipStream_t)stream);
 }
 extern "C" int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
                                  float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream)
 {
+    if (!qkv || !dout || !out || !lse || !dqkv) return EBC_E_ARG;
     return ebc::attention_bwd(dtype, qkv, dout, out, lse, delta_ws, dqkv, B, L, H, (hipStream_t)stream);
 }
 extern "C" int ebc_head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
                             float* logits, float* expo, int P, int HW, int NB, int embed, ebc_stream_t stream)
 {
+    if (!Z || !text || !logit_scale || !anchors || !logits || !expo) return EBC_E_ARG;
+    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
     return ebc::head_fwd(dtype_z, Z, text, logit_scale, anchors, logits, expo, P, HW, NB, embed, (hipStream_t)stream);
 }
 extern "C" size_t ebc_head_bwd_workspace_bytes(int P, int embed)
@@ -417,6 +431,8 @@ extern "C" int ebc_head_bwd(int dtype_z, int dtype_dz, const void* Z, const floa
                             float* dbias, float* dscale, int P, int HW, int NB, int embed, void* workspace,
                             size_t workspace_bytes, ebc_stream_t stream)
 {
+    if (!Z || !text || !logit_scale || !anchors || !dlogits || !dexp || !dZ) return EBC_E_ARG;
+    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
     return ebc::head_bwd(dtype_z, dtype_dz, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dZ, dbias, dscale, P, HW,
                          NB, embed, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -427,5 +443,6 @@ extern "C" int ebc_im2col(int dtype, const float* x, void* out, int B, int H, in
 }
 extern "C" int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream)
 {
+    if (!in || !out) return EBC_E_ARG;
     return ebc::cast_f32(dtype, in, out, n, (hipStream_t)stream);
 }

@@ -189,7 +189,14 @@ int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int dtype, voi
 
 /* LayerNorm over 768 channels (models/clip/_clip/blocks.py:8-14, fp32 math, eps 1e-5).
  * Row r of the output reads input row (r / rows_per_group) * group_stride + group_offset +
- * r % rows_per_group (rows_per_group = 0: identity), e.g. ln_post on the patch rows only. */
+ * r % rows_per_group (rows_per_group = 0: identity), e.g. ln_post on the patch rows only.
+ * The map is one-sided: the forward reads x at the mapped row and writes out / out_f32 / mean / rstd dense (row r);
+ * the backward reads dy, mean and rstd dense, and reads x and dx_in, and writes dx_out and dx_out_t, at the mapped
+ * row (rows outside the groups are not written).  M need not be a multiple of rows_per_group.
+ * Optional (NULL): one of out / out_f32, mean together with rstd (rstd alone is never written), dx_in (taken as 0),
+ * dx_out_t.  dy_f32 != 0: dy is f32 whatever dtype is (dtype f32: always).
+ * EBC_E_ARG, before any device work: NULL x / gamma / beta, out and out_f32 both NULL, mean without rstd; NULL dy / mean /
+ * rstd / dx_out; rows_per_group > 0 with group_offset < 0 or group_offset + rows_per_group > group_stride. */
 int ebc_layernorm_fwd(int dtype, const float* x, int rows_per_group, int group_stride, int group_offset,
                       const float* gamma, const float* beta, void* out, float* out_f32, float* mean,
                       float* rstd, int M, int D, ebc_stream_t stream);
@@ -201,7 +208,11 @@ int ebc_layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int
  * blocks.py:35-37): out [B*L, H*64], lse [B,H,L]; backward writes dqkv [B*L, 3*H*64].
  * L <= 256: K/V (and Q/dO) resident in LDS, one workgroup per (crop, head); 256 < L <= 16384 (the position
  * embedding interpolated for larger inputs, image_encoder.py:183-198): K/V streamed through LDS in 256-row chunks
- * with an online softmax; longer sequences return EBC_E_UNSUPPORTED. */
+ * with an online softmax; longer sequences return EBC_E_UNSUPPORTED.
+ * lse may be NULL in the forward.  delta_ws [B,H,L] f32 (rowsum(dout * out)) is written and read by the f32 backward
+ * at every L (its dQ kernel publishes it for the dK/dV kernel) and by the streamed backward (L > 256) of every dtype:
+ * there NULL is EBC_E_ARG.  The 16-bit backward at L <= 256 (one workgroup per (crop, head), delta kept in LDS) never
+ * touches it and takes NULL.  NULL qkv / out (forward) or qkv / dout / out / lse / dqkv (backward): EBC_E_ARG. */
 int ebc_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream);
 int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
                       float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream);
@@ -212,7 +223,10 @@ int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* 
  * upstream gradients (NULL = 1).  d bias / d logit_scale are summed deterministically (per-block partials in `workspace`,
  * ebc_head_bwd_workspace_bytes(P, embed) bytes, reduced in block order); workspace may be NULL when both are NULL.
  * Replaces the autograd backward of model.py:198-217 (F.normalize, cosine logits x exp(logit_scale), softmax, expectation)
- * and the projection bias's column sum. */
+ * and the projection bias's column sum.
+ * EBC_E_ARG, before any device work: P <= 0, HW <= 0 or P % HW != 0 (P is B whole images); NULL Z / text / logit_scale /
+ * anchors / logits / expo (forward) or Z / text / logit_scale / anchors / dlogits / dexp / dZ (backward); dbias or dscale
+ * given with a workspace that is NULL or too small.  ebc_cast_f32: NULL in / out, n % 4 != 0. */
 int ebc_head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
                  float* logits, float* expo, int P, int HW, int NB, int embed, ebc_stream_t stream);
 size_t ebc_head_bwd_workspace_bytes(int P, int embed);

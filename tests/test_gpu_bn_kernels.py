@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 import _bn_refs as R
+from _kernel_checks import GUARD_ROWS, SENT, _Hold, _elem, _exact, _f32, _guard_ok, _guarded, _report
 from conftest import rel_l2
 from ebc_amd import _lib
 
@@ -31,8 +32,6 @@ U = R.U32
 D53 = 2.0 ** -53
 EPS = float(torch.tensor(1e-5, dtype=torch.float32))       # the kernels take eps / momentum as C floats
 MOM = float(torch.tensor(0.1, dtype=torch.float32))
-SENT = 7.0
-GUARD_ROWS = 64
 EBC_E_ARG, EBC_E_UNSUPPORTED = -1, -3
 
 
@@ -53,19 +52,6 @@ def _randn(shape, seed):
     return torch.randn(tuple(shape), generator=_gen(seed), dtype=F64)
 
 
-def _f32(t):
-    return t.to(torch.float32).cuda().contiguous()
-
-
-class _Hold(list):
-    """Device copies of a call's operands, kept alive until the test has read the results."""
-
-    def __call__(self, t, f32=False):
-        d = _f32(t) if f32 else t.cuda()
-        self.append(d)
-        return _lib.ptr(d)
-
-
 hold = _Hold()
 
 
@@ -73,38 +59,6 @@ hold = _Hold()
 def _release_operands():
     yield
     hold.clear()
-
-
-def _guarded(rows, cols, dt, fill=SENT):
-    """[rows + GUARD_ROWS][cols] device tensor full of the sentinel; the kernel may only write the first `rows`."""
-    return torch.full((rows + GUARD_ROWS, cols), fill, dtype=dt, device="cuda")
-
-
-def _guard_ok(t, rows, fill=SENT):
-    return bool((t[rows:] == fill).all())
-
-
-def _report(name, err, bound):
-    ratio = float((err / bound).max())
-    print(f"RATIO {name} {ratio:.4f}")
-    assert ratio <= 1.0, (name, ratio, int((err / bound).argmax()))     # NaN fails too
-
-
-def _elem(name, out, ref, A, k, dt, extra=None):
-    """|out - ref| <= ulp_T(ref)/2 + k * 2^-24 * A per element."""
-    out = out.detach().to(F64).cpu().reshape(ref.shape)
-    bound = 0.5 * R.ulp(ref, dt) + k * U * A
-    if extra is not None:
-        bound = bound + extra
-    _report(name, (out - ref).abs(), bound)
-
-
-def _exact(out, ref, dt):
-    """Dyadic inputs: the reference is exact in f32, the stored value is it rounded once to T."""
-    assert torch.equal(ref.to(torch.float32).to(F64), ref), "the reference is not exact in f32: not a dyadic case"
-    want = ref.to(torch.float32).to(dt)
-    got = out.detach().cpu().reshape(want.shape)
-    assert torch.equal(got, want), int((got != want).sum())
 
 
 # ----------------------------------------------------------------------------------------------- reductions
