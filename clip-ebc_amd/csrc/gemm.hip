@@ -1717,6 +1717,8 @@ int gemm_nt(int dtype, int epi, int out_f32, const void* A, const void* B, void*
 {
     const int bk = dtype == EBC_F32 ? 32 : 64;
     if (M <= 0 || N <= 0 || K <= 0 || K % bk != 0 || N % 64 != 0 || !A || !B || !C) return EBC_E_ARG;
+    // the public epilogues only: dispatch_epi also knows the LayerNorm-fold ids, whose operands only gemm_nt_ln sets
+    if (epi < EPI_STORE || epi > EPI_GELU_BWD) return EBC_E_ARG;
     if ((epi == EPI_RESID && !resid) || (epi == EPI_GELU_BWD && !aux)) return EBC_E_ARG;
     if (a_rpg < 0 || (a_rpg > 0 && (a_goff < 0 || a_goff + a_rpg > a_gstride || epi != EPI_STORE))) return EBC_E_ARG;
     GemmArgs g{A, B, C, bias, resid, aux, M, N, K};
@@ -1896,6 +1898,26 @@ extern "C" int ebc_gemm(int dtype, int epilogue, int out_f32, const void* A, con
                         ebc_stream_t stream)
 {
     return ebc::gemm_nt(dtype, epilogue, out_f32, A, B, C, bias, resid, aux, M, N, K, (hipStream_t)stream);
+}
+
+extern "C" int ebc_gemm_rows(int dtype, int out_f32, const void* A, const void* B, void* C, const float* bias, int M, int N,
+                             int K, int rows_per_group, int group_stride, int group_offset, ebc_stream_t stream)
+{
+    return ebc::gemm_nt(dtype, EPI_STORE, out_f32, A, B, C, bias, nullptr, nullptr, M, N, K, (hipStream_t)stream,
+                        rows_per_group, group_stride, group_offset);
+}
+
+extern "C" int ebc_gemm_wgrad_tile_config(int dtype, int M, int N, int K, int* out)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || (dtype != EBC_F32 && dtype != EBC_F16 && dtype != EBC_BF16)) return EBC_E_ARG;
+    const WPlan wp = wgrad_plan(dtype != EBC_F32, false, M, N, K);
+    const TileCfg* c = find_cfg(wp.cfg);
+    if (out) {
+        out[0] = c->bm;
+        out[1] = c->bn;
+        out[2] = wp.partials ? -wp.splits : wp.splits;
+    }
+    return wp.cfg;
 }
 
 extern "C" int ebc_gemm_tile_config(int dtype, int M, int N, int K, int* out)

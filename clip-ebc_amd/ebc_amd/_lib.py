@@ -72,7 +72,9 @@ SIGNATURES = {
     "ebc_sinkhorn_workspace_bytes": (_Z, [_I, _I]),
     "ebc_sinkhorn": (_I, [_P, _P, _P, _I, _I, _F, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ebc_gemm": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ebc_gemm_rows": (_I, [_I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ebc_gemm_tile_config": (_I, [_I, _I, _I, _I, _P]),
+    "ebc_gemm_wgrad_tile_config": (_I, [_I, _I, _I, _I, _P]),
     "ebc_conv_tile_config": (_I, [_I, _I, _I, _I, _I, _P]),
     "ebc_gemm_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ebc_gemm_wgrad": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),

@@ -109,10 +109,22 @@ int ebc_sinkhorn(const float* a, const float* b, const float* C, int na, int nb,
  *   epilogue 2 RESID:    C = resid(f32) + acc + bias          (C f32: the residual stream, may be in place;
  *                                                              C in dtype when !out_f32)
  *   epilogue 3 GELU_BWD: C = acc * QuickGELU'(aux)           (MLP backward, dX only)
+ * bias may be NULL (none); aux may be NULL for GELU (the pre-activation is not kept).
+ * EBC_E_ARG, before any device work: an epilogue outside EBC_EPI_STORE .. EBC_EPI_GELU_BWD, a dtype that is none of
+ * EBC_F32 / EBC_F16 / EBC_BF16, M, N or K <= 0, K % 64 (K % 32 for f32) or N % 64 nonzero, NULL A / B / C, RESID
+ * without resid, GELU_BWD without aux.  EBC_E_UNSUPPORTED, before any device work: GELU or GELU_BWD with out_f32 on
+ * a 16-bit dtype.
  */
 enum { EBC_EPI_STORE = 0, EBC_EPI_GELU = 1, EBC_EPI_RESID = 2, EBC_EPI_GELU_BWD = 3 };
 int ebc_gemm(int dtype, int epilogue, int out_f32, const void* A, const void* B, void* C,
              const float* bias, const float* resid, void* aux, int M, int N, int K, ebc_stream_t stream);
+/* The STORE product with a row-mapped A operand: output row r reads A row
+ * (r / rows_per_group) * group_stride + group_offset + r % rows_per_group (rows_per_group 0: row r), e.g. the prompt
+ * rows 1 .. P of every crop's L token rows (rows_per_group P, group_stride L, group_offset 1).  C [M][N] is dense.
+ * EBC_E_ARG, before any device work: what ebc_gemm rejects, rows_per_group < 0, and rows_per_group > 0 with
+ * group_offset < 0 or group_offset + rows_per_group > group_stride. */
+int ebc_gemm_rows(int dtype, int out_f32, const void* A, const void* B, void* C, const float* bias, int M, int N, int K,
+                  int rows_per_group, int group_stride, int group_offset, ebc_stream_t stream);
 /* The tile configuration ebc_gemm dispatches for this shape (host-only, no device work): returns the
  * configuration id (> 0; a function of dtype and shape alone) and writes out[3] = {tile rows, tile columns, 1}
  * (these products never split K).  Lets tests pin which kernel instance a shape runs. */
@@ -122,12 +134,21 @@ int ebc_gemm_tile_config(int dtype, int M, int N, int K, int* out);
  * projection's dW = dZ^T Y of models/clip/model.py:91-95 (nn.Conv2d 1x1 backward).  Splits K over
  * workgroups (deterministic last-arriver sum).  `workspace` (>= ebc_gemm_wgrad_workspace_bytes; 0 = no
  * split for this shape) must be zero-filled before its first use and is then owned by the stream: every
- * call leaves its leading 16 KiB counter block zero again, the rest is scratch. */
+ * call leaves its leading 16 KiB counter block zero again, the rest is scratch.
+ * EBC_E_ARG, before any device work: NULL A / B / C, a bad dtype, M, N or K <= 0, K % 64 (K % 32 for f32) or N % 64
+ * nonzero, and a shape whose plan splits K with a workspace that is NULL or smaller than
+ * ebc_gemm_wgrad_workspace_bytes. */
 size_t ebc_gemm_wgrad_workspace_bytes(int dtype, int M, int N, int K);
 int ebc_gemm_wgrad(int dtype, const void* A, const void* B, float* C, int M, int N, int K,
                    void* workspace, size_t workspace_bytes, ebc_stream_t stream);
+/* The plan ebc_gemm_wgrad runs for this shape (host-only, no device work; mirrors ebc_gemm_tile_config): returns the
+ * tile configuration id and writes out[3] = {tile rows, tile columns, splits}: splits 1 = K is not split, 2 = two
+ * pieces summed by the last one to arrive, negative = -splits pieces stored as f32 partials and summed by a reduce
+ * launch. */
+int ebc_gemm_wgrad_tile_config(int dtype, int M, int N, int K, int* out);
 /* out[c][r] = in[r][c] for in [R][C] (16-bit or f32 elements; C and the output row stride ld_out >= R
- * multiples of 8, any R): the K-contiguous operand copies for ebc_gemm_wgrad. */
+ * multiples of 8, any R): the K-contiguous operand copies for ebc_gemm_wgrad.  Columns r >= R of out are left as they
+ * are.  EBC_E_ARG, before any device work: NULL in / out, a bad dtype, R or C <= 0, C % 8, ld_out < R, ld_out % 8. */
 int ebc_transpose(int dtype, const void* in, void* out, int R, int C, long ld_out, ebc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""Helpers shared by the per-kernel GPU modules (test_gpu_bn_kernels.py, test_gpu_encoder_kernels.py): sentinel-guarded
+"""Helpers shared by the per-kernel GPU modules (test_gpu_bn_kernels.py, test_gpu_encoder_kernels.py,
+test_gpu_gemm_kernels.py): sentinel-guarded
 output buffers, operand lifetime, and the per-element checks that print "RATIO <name> <largest error / bound>" before
 they assert."""
 import torch
@@ -34,6 +35,20 @@ def _guard_ok(t, rows, fill=SENT):
     return bool((t[rows:] == fill).all())
 
 
+class _Framed:
+    """[GUARD_ROWS + rows + GUARD_ROWS][cols] device tensor full of the sentinel; `mid` (what the kernel is given) is
+    the `rows` in the middle, so a write before the first row or past the last lands on a guard."""
+
+    def __init__(self, rows, cols, dt, fill=SENT):
+        self.rows, self.fill = rows, fill
+        self.full = torch.full((rows + 2 * GUARD_ROWS, cols), fill, dtype=dt, device="cuda")
+        self.mid = self.full[GUARD_ROWS:GUARD_ROWS + rows]
+
+    def ok(self):
+        lo, hi = self.full[:GUARD_ROWS], self.full[GUARD_ROWS + self.rows:]
+        return bool((lo == self.fill).all()) and bool((hi == self.fill).all())
+
+
 def _report(name, err, bound):
     ratio = float((err / bound).max())
     print(f"RATIO {name} {ratio:.4f}")
@@ -53,5 +68,5 @@ def _exact(out, ref, dt):
     """Dyadic inputs: the reference is exact in f32, the stored value is it rounded once to T."""
     assert torch.equal(ref.to(torch.float32).to(F64), ref), "the reference is not exact in f32: not a dyadic case"
     want = ref.to(torch.float32).to(dt)
-    got = out.detach().cpu().reshape(want.shape)
+    got = out.detach().to(want.device).reshape(want.shape)       # (a reference kept on the device is compared there)
     assert torch.equal(got, want), int((got != want).sum())

@@ -130,6 +130,141 @@ def test_head_outputs_and_cast_reject_without_device(lib):
     assert lib.ebc_cast_f32(F16, _X, None, 8, None) == EBC_E_ARG
 
 
+EBC_E_UNSUPPORTED = -3
+BF16 = 2
+STORE, GELU, RESID, GELU_BWD = 0, 1, 2, 3
+
+
+def _gemm(lib, dtype=F16, epi=STORE, out_f32=0, A=_X, B=_X, C=_X, bias=None, resid=None, aux=None, M=16, N=64, K=64):
+    return lib.ebc_gemm(dtype, epi, out_f32, A, B, C, bias, resid, aux, M, N, K, None)
+
+
+@pytest.mark.parametrize("dtype", [F32, F16, BF16])
+@pytest.mark.parametrize("epi", [-1, 4, 5, 6, 7, 8, 9, 1 << 20])
+def test_gemm_rejects_internal_epilogue_ids_without_device(lib, dtype, epi):
+    """Only EBC_EPI_STORE .. EBC_EPI_GELU_BWD are public: the LayerNorm-fold ids 6, 7 and 8 used to reach a kernel whose
+    fold operands were all NULL.  Every operand is a bogus pointer here, so a call that launched would not return."""
+    assert _gemm(lib, dtype=dtype, epi=epi, resid=_X, aux=_X, bias=_X) == EBC_E_ARG
+    assert _gemm(lib, dtype=dtype, epi=epi, out_f32=1, resid=_X, aux=_X, bias=_X) == EBC_E_ARG
+
+
+@pytest.mark.parametrize("kw", [dict(A=None), dict(B=None), dict(C=None), dict(K=48), dict(K=96), dict(K=0), dict(N=96),
+                                dict(N=32), dict(N=0), dict(M=0), dict(M=-3), dict(dtype=F32, K=48), dict(dtype=F32, K=16),
+                                dict(epi=RESID), dict(epi=RESID, out_f32=1), dict(epi=GELU_BWD),
+                                dict(dtype=F32, epi=RESID), dict(dtype=F32, epi=GELU_BWD), dict(dtype=3), dict(dtype=-1),
+                                dict(dtype=7, epi=RESID, resid=_X)])
+def test_gemm_rejects_without_device(lib, kw):
+    """NULL A / B / C, K % 64 (16-bit) and K % 32 (f32), N % 64, empty shapes, RESID without resid, GELU' without aux,
+    a dtype that is none of the three."""
+    assert _gemm(lib, **kw) == EBC_E_ARG
+    assert _gemm(lib, **{"dtype": BF16, **kw}) == EBC_E_ARG
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16])
+@pytest.mark.parametrize("epi", [GELU, GELU_BWD])
+def test_gemm_gelu_to_f32_is_unsupported_without_device(lib, dtype, epi):
+    assert _gemm(lib, dtype=dtype, epi=epi, out_f32=1, aux=_X) == EBC_E_UNSUPPORTED
+
+
+def _rows(lib, dtype=F16, out_f32=0, A=_X, B=_X, C=_X, bias=None, M=15, N=768, K=768, rpg=5, gs=23, go=1):
+    return lib.ebc_gemm_rows(dtype, out_f32, A, B, C, bias, M, N, K, rpg, gs, go, None)
+
+
+@pytest.mark.parametrize("kw", [dict(A=None), dict(B=None), dict(C=None), dict(K=800), dict(dtype=F32, K=48), dict(N=800),
+                                dict(M=0), dict(dtype=5), dict(rpg=-1), dict(go=-1), dict(go=19), dict(rpg=24),
+                                dict(rpg=1, gs=0, go=0), dict(rpg=196, gs=229, go=34)])
+def test_gemm_rows_rejects_without_device(lib, kw):
+    """ebc_gemm's checks, and a row map that leaves its group."""
+    assert _rows(lib, **kw) == EBC_E_ARG
+
+
+def _wgrad(lib, dtype=F16, A=_X, B=_X, C=_X, M=128, N=64, K=64, ws=None, wsb=0):
+    return lib.ebc_gemm_wgrad(dtype, A, B, C, M, N, K, ws, wsb, None)
+
+
+@pytest.mark.parametrize("kw", [dict(A=None), dict(B=None), dict(C=None), dict(K=96), dict(dtype=F32, K=48), dict(N=96),
+                                dict(M=0), dict(N=0), dict(K=0), dict(dtype=3), dict(dtype=-2)])
+def test_gemm_wgrad_rejects_without_device(lib, kw):
+    assert _wgrad(lib, **kw) == EBC_E_ARG
+
+
+@pytest.mark.parametrize("dtype", [F32, F16, BF16])
+@pytest.mark.parametrize("M,N,K", [(100, 192, 1024), (100, 192, 4096), (300, 1024, 25088)])
+def test_gemm_wgrad_rejects_a_split_plan_without_its_workspace(lib, dtype, M, N, K):
+    """A shape whose plan splits K (two pieces, or partials and a reduce launch): NULL workspace, one that is a byte
+    short, NULL with a size."""
+    import ctypes
+    out = (ctypes.c_int * 3)()
+    assert lib.ebc_gemm_wgrad_tile_config(dtype, M, N, K, out) > 0
+    need = lib.ebc_gemm_wgrad_workspace_bytes(dtype, M, N, K)
+    if abs(out[2]) == 1:
+        assert need == 0                                     # (the f32 plan of a shape need not split)
+        return
+    assert need > 16 * 1024
+    assert _wgrad(lib, dtype=dtype, M=M, N=N, K=K, ws=None, wsb=0) == EBC_E_ARG
+    assert _wgrad(lib, dtype=dtype, M=M, N=N, K=K, ws=None, wsb=need) == EBC_E_ARG
+    assert _wgrad(lib, dtype=dtype, M=M, N=N, K=K, ws=_X, wsb=need - 1) == EBC_E_ARG
+    assert _wgrad(lib, dtype=dtype, M=M, N=N, K=K, ws=_X, wsb=0) == EBC_E_ARG
+
+
+def test_gemm_wgrad_tile_config_is_host_only(lib):
+    import ctypes
+    out = (ctypes.c_int * 3)()
+    assert lib.ebc_gemm_wgrad_tile_config(F16, 128, 64, 64, out) == 2 and tuple(out) == (128, 64, 1)
+    assert lib.ebc_gemm_wgrad_tile_config(F32, 128, 64, 64, None) == 2
+    for bad in (dict(dtype=3), dict(M=0), dict(N=-1), dict(K=0)):
+        a = {"dtype": F16, "M": 128, "N": 64, "K": 64, **bad}
+        assert lib.ebc_gemm_wgrad_tile_config(a["dtype"], a["M"], a["N"], a["K"], out) == EBC_E_ARG
+    # a split plan's workspace is the counter block plus what the plan's pieces need
+    for dt in (F32, F16, BF16):
+        for M, N, K in ((100, 192, 1024), (100, 192, 4096), (300, 384, 8192), (300, 1024, 25088)):
+            cfg = lib.ebc_gemm_wgrad_tile_config(dt, M, N, K, out)
+            bm, bn, sp = tuple(out)
+            tiles = -(-M // bm) * (N // bn)
+            want = 0 if abs(sp) == 1 else 16384 + (-sp * M * N * 4 if sp < 0 else sp * tiles * bm * bn * 4)
+            assert cfg in (1, 2, 3, 7) and N % bn == 0 and lib.ebc_gemm_wgrad_workspace_bytes(dt, M, N, K) == want
+
+
+def test_gpu_gemm_case_lists_reach_every_tile_and_plan_class(lib):
+    """The shapes of tests/test_gpu_gemm_kernels.py against the host-only dispatch calls, so a dispatch change that moves
+    a case onto another kernel shows without a GPU: every tile id ebc_gemm can return and every (tile, split class) of
+    ebc_gemm_wgrad has a case, except the classes the planner never picks."""
+    import ctypes
+    import test_gpu_gemm_kernels as T
+    out = (ctypes.c_int * 3)()
+    for dt, cases in ((F32, T.CASES32), (F16, T.CASES16), (BF16, T.CASES16)):
+        for tile, M, N, K in cases:
+            assert lib.ebc_gemm_tile_config(dt, M, N, K, out) == tile and tuple(out) == (*T.TILES[tile][:2], 1), (dt, M, N, K)
+    assert {c[0] for c in T.CASES16} == set(T.TILES) == {1, 2, 3, 4, 5, 7, 15, 16} and {c[0] for c in T.CASES32} == {2}
+    reachable = set()
+    for M in (1, 129, 1000, 3664, 4097, 7328, 8065, 12544, 24321, 32060, 50176):
+        for N in range(64, 4097, 64):
+            for K in (64, 512, 768, 1024, 2304, 3072, 4096, 8192):
+                reachable.add(lib.ebc_gemm_tile_config(F16, M, N, K, None))
+    assert reachable == set(T.TILES)
+
+    def split_class(s):
+        return min(abs(s), 3)                       # 1: no split, 2: last arriver, 3: partials and a reduce launch
+
+    for dt, plans in ((F32, T.WGRAD32), (F16, T.WGRAD16), (BF16, T.WGRAD16)):
+        for (M, N, K), plan in plans:
+            assert (lib.ebc_gemm_wgrad_tile_config(dt, M, N, K, out), out[2]) == plan, (dt, M, N, K)
+            assert (out[2] < 0) == (abs(out[2]) > 2)
+    assert {(p[0], split_class(p[1])) for _, p in T.WGRAD16} == {(t, c) for t in (1, 2, 3, 7) for c in (1, 2, 3)}
+    assert {(p[0], split_class(p[1])) for _, p in T.WGRAD32} == {(2, 1), (2, 2), (2, 3)}
+
+
+def _transpose(lib, dtype=F16, src=_X, out=_X, R=9, C=72, ld=16):
+    return lib.ebc_transpose(dtype, src, out, R, C, ld, None)
+
+
+@pytest.mark.parametrize("kw", [dict(src=None), dict(out=None), dict(R=0), dict(C=0), dict(C=-8), dict(C=68), dict(C=4),
+                                dict(ld=8), dict(R=17), dict(ld=20), dict(ld=12), dict(dtype=3), dict(dtype=-1)])
+def test_transpose_rejects_without_device(lib, kw):
+    """NULL in / out, empty shapes, C % 8, ld_out < R, ld_out % 8, a bad dtype."""
+    assert _transpose(lib, **kw) == EBC_E_ARG
+
+
 def test_product_has_no_cpu_fallback():
     """The product path refuses to run without a HIP device rather than falling back."""
     import torch
