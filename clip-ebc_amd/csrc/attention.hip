@@ -167,30 +167,15 @@ __device__ __forceinline__ typename E::Frag lds_rowfrag(const typename E::T* bas
 // reductions across the four 16-lane rows by v_permlane16_swap / v_permlane32_swap (each lane receives its own and its
 // partner's value, in either order, so max / + of the pair is the same on both lanes).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// softmax pair arithmetic as two single-lane instructions (EBC_ATTN_SCALAR 1; the Makefile builds this file with
-// -fno-slp-vectorize so they stay single) or packed f32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32, 0).  Beside the
+// softmax pair arithmetic as two single-lane instructions (the Makefile builds this file with -fno-slp-vectorize so
+// they stay single), not packed f32 (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32).  Beside the
 // MFMAs a packed f32 instruction costs more issue than the two it replaces (MI355X_MICROARCH.md per-instruction
 // constants); r06, tools/lab/attn_tl_lab.hip, 16 crops: forward 11.8 -> 11.5 us, backward 25.3 -> 24.7 us
-#ifndef EBC_ATTN_SCALAR
-#define EBC_ATTN_SCALAR 1
-#endif
-// backward: the MFMA chain of dP starts from -delta (cdna_hip_programming.md "row constants as the initial accumulator"),
-// so dS = p dP' needs no subtraction (r06: backward 24.7 -> 24.0 us, compute phase 14.9 -> 14.3 us)
-#ifndef EBC_ATTN_DINIT
-#define EBC_ATTN_DINIT 1
-#endif
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) {
-    if constexpr (EBC_ATTN_SCALAR) return f32x2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)};
-    else return __builtin_elementwise_fma(a, b, c);
+    return f32x2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)};
 }
-__device__ __forceinline__ f32x2 add2(f32x2 a, f32x2 b) {
-    if constexpr (EBC_ATTN_SCALAR) return f32x2{a.x + b.x, a.y + b.y};
-    else return a + b;
-}
-__device__ __forceinline__ f32x2 mul2(f32x2 a, f32x2 b) {
-    if constexpr (EBC_ATTN_SCALAR) return f32x2{a.x * b.x, a.y * b.y};
-    else return a * b;
-}
+__device__ __forceinline__ f32x2 add2(f32x2 a, f32x2 b) { return f32x2{a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ f32x2 mul2(f32x2 a, f32x2 b) { return f32x2{a.x * b.x, a.y * b.y}; }
 __device__ __forceinline__ float max3f(float a, float b, float c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }
@@ -743,7 +728,9 @@ __global__ __launch_bounds__(1024) void attn_bwd_one_kernel(const typename E::T*
         f32x4 sv[2][2], pv[2][2];                              // [pair parity][tile of the pair]
         auto sdp = [&](int kt, f32x4& s_, f32x4& p_) {
             s_ = f32x4{0.f, 0.f, 0.f, 0.f};
-            p_ = EBC_ATTN_DINIT ? f32x4{-dq, -dq, -dq, -dq} : f32x4{0.f, 0.f, 0.f, 0.f};   // dP - delta from the MFMA chain
+            // the MFMA chain of dP starts from -delta (cdna_hip_programming.md "row constants as the initial accumulator"),
+            // so dS = p dP' needs no subtraction (r06: backward 24.7 -> 24.0 us, compute phase 14.9 -> 14.3 us)
+            p_ = f32x4{-dq, -dq, -dq, -dq};
             if (kt < nkt) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
@@ -764,7 +751,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_one_kernel(const typename E::T*
             }
             // packed f32 (softmax arithmetic note above the forward): p = 2^(s c - lse c), dS = p (dP - delta)
             float ds[8];
-            const f32x2 c2v = {c2, c2}, nlv = {-lq2, -lq2}, ndv = {-dq, -dq};
+            const f32x2 c2v = {c2, c2}, nlv = {-lq2, -lq2};
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 const int kt = 2 * st + hf;
@@ -775,8 +762,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_one_kernel(const typename E::T*
                     p.y = __builtin_amdgcn_exp2f(p.y);
                     if (kt >= nkt || (ragged && kt == nkt - 1 && 16 * kt + 4 * fg + i >= L)) p.x = 0.f;
                     if (kt >= nkt || (ragged && kt == nkt - 1 && 16 * kt + 4 * fg + i + 1 >= L)) p.y = 0.f;
-                    const f32x2 d = EBC_ATTN_DINIT ? mul2(p, f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]})
-                                                   : mul2(p, add2(f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]}, ndv));
+                    const f32x2 d = mul2(p, f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]});
                     ds[4 * hf + i] = d.x;
                     ds[4 * hf + i + 1] = d.y;
                 }
@@ -808,12 +794,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_one_kernel(const typename E::T*
         f32x4 sv[2][2], pv[2][2];                              // pipelined as the dQ phase, over query-tile pairs
         auto sdp = [&](int qt, f32x4& s_, f32x4& p_) {
             s_ = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (EBC_ATTN_DINIT) {                    // dP^T - delta of the tile's queries from the MFMA chain
-                const float4 d4 = *reinterpret_cast<const float4*>(dl + 16 * qt + 4 * fg);
-                p_ = f32x4{-d4.x, -d4.y, -d4.z, -d4.w};
-            } else {
-                p_ = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            const float4 d4 = *reinterpret_cast<const float4*>(dl + 16 * qt + 4 * fg);
+            p_ = f32x4{-d4.x, -d4.y, -d4.z, -d4.w};           // dP^T - delta of the tile's queries from the MFMA chain
             if (qt < nqt) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
@@ -838,16 +820,14 @@ __global__ __launch_bounds__(1024) void attn_bwd_one_kernel(const typename E::T*
             for (int hf = 0; hf < 2; ++hf) {
                 const int qt = 2 * st + hf;
                 const float4 l4 = *reinterpret_cast<const float4*>(ls + 16 * qt + 4 * fg);
-                const float4 d4 = *reinterpret_cast<const float4*>(dl + 16 * qt + 4 * fg);
-                const f32x2 lq[2] = {{l4.x, l4.y}, {l4.z, l4.w}}, dq[2] = {{d4.x, d4.y}, {d4.z, d4.w}};
+                const f32x2 lq[2] = {{l4.x, l4.y}, {l4.z, l4.w}};
 #pragma unroll
                 for (int i = 0; i < 4; i += 2) {
                     // lse = +inf (padding) -> p = 0
                     f32x2 p = fma2(f32x2{sv[cur][hf][i], sv[cur][hf][i + 1]}, c2v, -lq[i / 2]);
                     p.x = __builtin_amdgcn_exp2f(p.x);
                     p.y = __builtin_amdgcn_exp2f(p.y);
-                    const f32x2 d = EBC_ATTN_DINIT ? mul2(p, f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]})
-                                                   : mul2(p, add2(f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]}, -dq[i / 2]));
+                    const f32x2 d = mul2(p, f32x2{pv[cur][hf][i], pv[cur][hf][i + 1]});
                     pp[4 * hf + i] = p.x;
                     pp[4 * hf + i + 1] = p.y;
                     ds[4 * hf + i] = d.x;
@@ -1263,10 +1243,11 @@ template <class E, int NW, int LFIX, int QT = 1> int attn_fwd_nw(const void* qkv
     if (!ensure_lds<attn_fwd_kernel<E, NW, LFIX, QT>>((int)lds, st)) return EBC_E_LAUNCH;
     const int grid = B * H * ((L + 16 * NW * QT - 1) / (16 * NW * QT));
     const TouchList t = touch && g_touch_mode == 1 ? *touch : TouchList{};
-    const int pi = probe_on() ? probe_start(EBC_PROBE_ATTN_FWD, 0, 0, 0, 0, B, L, H, st) : -1;
-    hipLaunchKernelGGL((attn_fwd_kernel<E, NW, LFIX, QT>), dim3(grid), dim3(64 * NW), lds, st, (const typename E::T*)qkv,
-                       (typename E::T*)out, lse, B, L, H, 0.125f, t);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_ATTN_FWD, 0, 0, 0, 0, B, L, H, st);
+        hipLaunchKernelGGL((attn_fwd_kernel<E, NW, LFIX, QT>), dim3(grid), dim3(64 * NW), lds, st,
+                           (const typename E::T*)qkv, (typename E::T*)out, lse, B, L, H, 0.125f, t);
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -1288,16 +1269,19 @@ template <class E, int NW, int LFIX> int attn_bwd_nw(const void* qkv, const void
     if (!ensure_lds<attn_bwd_dq_kernel<E, NW, LFIX>>((int)lds_dq, st) || !ensure_lds<attn_bwd_dkv_kernel<E, NW, LFIX>>((int)lds_kv, st))
         return EBC_E_LAUNCH;
     const int grid = B * H * ((L + 16 * NW - 1) / (16 * NW));
-    int pi = probe_on() ? probe_start(EBC_PROBE_ATTN_BWD_DQ, 0, 0, 0, 0, B, L, H, st) : -1;
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<E, NW, LFIX>), dim3(grid), dim3(64 * NW), lds_dq, st, (const typename E::T*)qkv,
-                       (const typename E::T*)dout, (const typename E::T*)out, lse, delta, (typename E::T*)dqkv, B, L, H,
-                       0.125f);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_ATTN_BWD_DQ, 0, 0, 0, 0, B, L, H, st);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<E, NW, LFIX>), dim3(grid), dim3(64 * NW), lds_dq, st,
+                           (const typename E::T*)qkv, (const typename E::T*)dout, (const typename E::T*)out, lse, delta,
+                           (typename E::T*)dqkv, B, L, H, 0.125f);
+    }
     EBC_CHECK_LAUNCH();
-    pi = probe_on() ? probe_start(EBC_PROBE_ATTN_BWD_DKV, 0, 0, 0, 0, B, L, H, st) : -1;
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<E, NW, LFIX>), dim3(grid), dim3(64 * NW), lds_kv, st, (const typename E::T*)qkv,
-                       (const typename E::T*)dout, lse, delta, (typename E::T*)dqkv, B, L, H, 0.125f);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_ATTN_BWD_DKV, 0, 0, 0, 0, B, L, H, st);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<E, NW, LFIX>), dim3(grid), dim3(64 * NW), lds_kv, st,
+                           (const typename E::T*)qkv, (const typename E::T*)dout, lse, delta, (typename E::T*)dqkv, B, L, H,
+                           0.125f);
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -1308,11 +1292,12 @@ template <class E, int LFIX> int attn_bwd_one(const void* qkv, const void* dout,
     const size_t lds = 4 * C::TILE_BYTES + 2 * LP * sizeof(float);
     if (!ensure_lds<attn_bwd_one_kernel<E, LFIX>>((int)lds, st)) return EBC_E_LAUNCH;
     const TouchList t = touch && g_touch_mode == 1 ? *touch : TouchList{};
-    const int pi = probe_on() ? probe_start(EBC_PROBE_ATTN_BWD_DQ, 1, 0, 0, 0, B, L, H, st) : -1;
-    hipLaunchKernelGGL((attn_bwd_one_kernel<E, LFIX>), dim3(B * H), dim3(1024), lds, st, (const typename E::T*)qkv,
-                       (const typename E::T*)dout, (const typename E::T*)out, lse, (typename E::T*)dqkv, B, L, H, 0.125f,
-                       rows, t);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_ATTN_BWD_DQ, 1, 0, 0, 0, B, L, H, st);
+        hipLaunchKernelGGL((attn_bwd_one_kernel<E, LFIX>), dim3(B * H), dim3(1024), lds, st, (const typename E::T*)qkv,
+                           (const typename E::T*)dout, (const typename E::T*)out, lse, (typename E::T*)dqkv, B, L, H,
+                           0.125f, rows, t);
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -1352,19 +1337,10 @@ int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int 
 {
     if (L <= 0 || L > L_MAX || B <= 0 || H <= 0) return EBC_E_UNSUPPORTED;
     if (L > LP) {                                  // K / V streamed through LDS in chunks (no weight touch)
-        switch (dtype) {
-            case EBC_F32: return attn_fwd_long<EF32>(qkv, out, lse, B, L, H, st);
-            case EBC_F16: return attn_fwd_long<EF16>(qkv, out, lse, B, L, H, st);
-            case EBC_BF16: return attn_fwd_long<EBF16>(qkv, out, lse, B, L, H, st);
-        }
-        return EBC_E_ARG;
+        EBC_DTYPE_SWITCH(dtype, return attn_fwd_long<E>(qkv, out, lse, B, L, H, st));
     }
-    switch (dtype) {
-        case EBC_F32: return attn_fwd_t<EF32>(qkv, out, lse, B, L, H, st, nullptr);
-        case EBC_F16: return attn_fwd_t<EF16>(qkv, out, lse, B, L, H, st, touch);
-        case EBC_BF16: return attn_fwd_t<EBF16>(qkv, out, lse, B, L, H, st, touch);
-    }
-    return EBC_E_ARG;
+    // f32 (parity mode) issues no weight touch
+    EBC_DTYPE_SWITCH(dtype, return attn_fwd_t<E>(qkv, out, lse, B, L, H, st, E::BYTES == 2 ? touch : nullptr));
 }
 int attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse, float* delta,
                   void* dqkv, int B, int L, int H, hipStream_t st, int rows, const TouchList* touch)
@@ -1372,20 +1348,12 @@ int attention_bwd(int dtype, const void* qkv, const void* dout, const void* out,
     if (L <= 0 || L > L_MAX || B <= 0 || H <= 0 || rows < 0) return EBC_E_UNSUPPORTED;
     if (L > LP) {                                  // the two-role chunked pair; rows > 0 computes every row (a superset)
         if (!delta || !lse) return EBC_E_ARG;
-        switch (dtype) {
-            case EBC_F32: return attn_bwd_long<EF32>(qkv, dout, out, lse, delta, dqkv, B, L, H, st);
-            case EBC_F16: return attn_bwd_long<EF16>(qkv, dout, out, lse, delta, dqkv, B, L, H, st);
-            case EBC_BF16: return attn_bwd_long<EBF16>(qkv, dout, out, lse, delta, dqkv, B, L, H, st);
-        }
-        return EBC_E_ARG;
+        EBC_DTYPE_SWITCH(dtype, return attn_bwd_long<E>(qkv, dout, out, lse, delta, dqkv, B, L, H, st));
     }
     // the f32 dQ kernel publishes delta for the dK/dV kernel; the 16-bit one-workgroup kernel keeps it in LDS
     if (dtype == EBC_F32 && !delta) return EBC_E_ARG;
-    switch (dtype) {
-        case EBC_F32: return attn_bwd_t<EF32>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows, nullptr);
-        case EBC_F16: return attn_bwd_t<EF16>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows, touch);
-        case EBC_BF16: return attn_bwd_t<EBF16>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows, touch);
-    }
-    return EBC_E_ARG;
+    // ... and f32 issues no weight touch
+    EBC_DTYPE_SWITCH(dtype, return attn_bwd_t<E>(qkv, dout, out, lse, delta, dqkv, B, L, H, st, rows,
+                                                 E::BYTES == 2 ? touch : nullptr));
 }
 }  // namespace ebc

@@ -33,16 +33,10 @@ namespace {
 
 // threads per workgroup (16 waves, 4 per SIMD): r02 measured the 100-iteration floor at 512 and 1024 threads the same,
 // 256 threads 1.5x slower; 1024 keeps one pass over the cells / blocks per phase at G = 28
-#ifndef EBC_DACE_NT
-#define EBC_DACE_NT 1024
-#endif
-constexpr int NT = EBC_DACE_NT;
+constexpr int NT = 1024;
 constexpr int LDS_MAX = 160 * 1024;
 constexpr float M_EPS = 1e-16f;          // bregman_pytorch.py:8
-#ifndef EBC_DACE_W16_MIN
-#define EBC_DACE_W16_MIN 257
-#endif
-constexpr int SORTED_W16_MIN_POINTS = EBC_DACE_W16_MIN;   // crops from this many points: 16 lanes per block (r02 probe)
+constexpr int SORTED_W16_MIN_POINTS = 257;   // crops from this many points: 16 lanes per block (r02 probe)
 constexpr float EPS = 1e-8f;             // dm_loss.py:7
 
 // Lab-only phase timer (-DEBC_DACE_PROF, tools/dbg/dace_prof.py): thread 0 of each crop's workgroup records core-clock
@@ -999,9 +993,10 @@ template <int G> int launch(const Params& P0, hipStream_t st)
     P.lds_cap_s = (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT));
     P.lds_cap_c = (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT_C));
     if (!ensure_lds<dace_loss_kernel<G>>(LDS_MAX, st)) return EBC_E_LAUNCH;
-    const int pi = probe_on() ? probe_start(EBC_PROBE_DACE, P.count_mode, 0, 0, 0, P.B, P.total_points, G, st) : -1;
-    hipLaunchKernelGGL(dace_loss_kernel<G>, dim3(P.B), dim3(NT), LDS_MAX, st, P);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_DACE, P.count_mode, 0, 0, 0, P.B, P.total_points, G, st);
+        hipLaunchKernelGGL(dace_loss_kernel<G>, dim3(P.B), dim3(NT), LDS_MAX, st, P);
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }

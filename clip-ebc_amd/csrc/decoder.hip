@@ -29,47 +29,12 @@
 #include "ebc_common.h"
 #include "mfma.h"
 #include "kernels.h"
+#include "vec_io.h"
 
 using namespace ebc;
 
 namespace {
 
-template <class T> __device__ __forceinline__ void st4(T* p, float4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, float4 v) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<h4*>(p) = h4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-}
-template <> __device__ __forceinline__ void st4<__bf16>(__bf16* p, float4 v) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<b4*>(p) = b4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-}
-template <class T> __device__ __forceinline__ float4 ld4(const T* p);
-template <> __device__ __forceinline__ float4 ld4<float>(const float* p) { return *reinterpret_cast<const float4*>(p); }
-template <> __device__ __forceinline__ float4 ld4<_Float16>(const _Float16* p) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    const h4 v = *reinterpret_cast<const h4*>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-template <> __device__ __forceinline__ float4 ld4<__bf16>(const __bf16* p) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    const b4 v = *reinterpret_cast<const b4*>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-// 8 consecutive elements (16 B for 16-bit types, 32 B for f32) <-> float[8]
-template <class T> __device__ __forceinline__ void ld8(const T* p, float* v) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const t8 x = *reinterpret_cast<const t8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)x[i];
-}
-template <class T> __device__ __forceinline__ void st8(T* p, const float* v) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 x;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = (T)v[i];
-    *reinterpret_cast<t8*>(p) = x;
-}
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 // 8 consecutive per-channel f32 parameters (two 16-B loads; c a multiple of 8)
 __device__ __forceinline__ void ldp8(const float* p, float* v) {
@@ -993,14 +958,6 @@ int bn_stats_t(const void* z, double* colsum, void* ws, size_t wsb, long P, int 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------- C-ABI
-#define EBC_DTYPE_SWITCH(dtype, ...)                                   \
-    switch (dtype) {                                                   \
-        case EBC_F32: { using T = float; __VA_ARGS__; } break;         \
-        case EBC_F16: { using T = _Float16; __VA_ARGS__; } break;      \
-        case EBC_BF16: { using T = __bf16; __VA_ARGS__; } break;       \
-        default: return EBC_E_ARG;                                     \
-    }
-
 extern "C" int ebc_dec_geometry(int dtype, int B, int H, int W, int C, long* out)
 {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 64 || !out) return EBC_E_ARG;
@@ -1143,12 +1100,7 @@ extern "C" int ebc_bn_bwd_reduce(int dtype, const void* gy, const void* mask_y, 
     if (!gy || !z || !mean || !rstd || !sums || P <= 0 || C <= 0 || (!mask_y && (!scale || !shift))) return EBC_E_ARG;
     if (C % 8) return EBC_E_UNSUPPORTED;          // one 8-channel vector per thread (bn_bwd_partial_kernel)
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: return bn_bwd_reduce_t<float>(gy, mask_y, z, mean, rstd, scale, shift, sums, ws, wsb, P, C, st);
-        case EBC_F16: return bn_bwd_reduce_t<_Float16>(gy, mask_y, z, mean, rstd, scale, shift, sums, ws, wsb, P, C, st);
-        case EBC_BF16: return bn_bwd_reduce_t<__bf16>(gy, mask_y, z, mean, rstd, scale, shift, sums, ws, wsb, P, C, st);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return bn_bwd_reduce_t<T>(gy, mask_y, z, mean, rstd, scale, shift, sums, ws, wsb, P, C, st));
 }
 
 extern "C" int ebc_bn_bwd_finalize(const double* sums, double count, const float* gamma, const float* rstd,
@@ -1251,12 +1203,7 @@ extern "C" int ebc_bn_stats(int dtype, const void* z, double* colsum, void* ws, 
 {
     if (!z || !colsum || P <= 0 || C % 8) return EBC_E_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: return bn_stats_t<float>(z, colsum, ws, wsb, P, C, st);
-        case EBC_F16: return bn_stats_t<_Float16>(z, colsum, ws, wsb, P, C, st);
-        case EBC_BF16: return bn_stats_t<__bf16>(z, colsum, ws, wsb, P, C, st);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return bn_stats_t<T>(z, colsum, ws, wsb, P, C, st));
 }
 
 extern "C" int ebc_bn_stats_finalize(int dtype, const void* z, void* ws, size_t wsb, long P, int C, float eps,
@@ -1268,12 +1215,7 @@ extern "C" int ebc_bn_stats_finalize(int dtype, const void* z, void* ws, size_t 
     if ((running_mean == nullptr) != (running_var == nullptr)) return EBC_E_ARG;
     const FwdFin fin{eps, momentum, gamma, beta, mean, rstd, scale, shift, running_mean, running_var, num_batches_tracked};
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: return bn_stats_t<float>(z, colsum_out, ws, wsb, P, C, st, &fin);
-        case EBC_F16: return bn_stats_t<_Float16>(z, colsum_out, ws, wsb, P, C, st, &fin);
-        case EBC_BF16: return bn_stats_t<__bf16>(z, colsum_out, ws, wsb, P, C, st, &fin);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return bn_stats_t<T>(z, colsum_out, ws, wsb, P, C, st, &fin));
 }
 
 extern "C" int ebc_bn_bwd_reduce_finalize(int dtype, const void* gy, const void* mask_y, const void* z, const float* mean,
@@ -1286,12 +1228,8 @@ extern "C" int ebc_bn_bwd_reduce_finalize(int dtype, const void* gy, const void*
     if (C % 8) return EBC_E_UNSUPPORTED;          // as ebc_bn_bwd_reduce
     const BwdFin fin{gamma, dgamma, dbeta, coef};
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: return bn_bwd_reduce_t<float>(gy, mask_y, z, mean, rstd, scale, shift, nullptr, ws, wsb, P, C, st, &fin);
-        case EBC_F16: return bn_bwd_reduce_t<_Float16>(gy, mask_y, z, mean, rstd, scale, shift, nullptr, ws, wsb, P, C, st, &fin);
-        case EBC_BF16: return bn_bwd_reduce_t<__bf16>(gy, mask_y, z, mean, rstd, scale, shift, nullptr, ws, wsb, P, C, st, &fin);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return bn_bwd_reduce_t<T>(gy, mask_y, z, mean, rstd, scale, shift, nullptr, ws, wsb, P, C, st,
+                                                      &fin));
 }
 
 extern "C" int ebc_bn_relu(int dtype, const void* z, const float* scale, const float* shift, void* out, long P, int C,

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/ebc_hip.h"
+#include "mfma.h"
 
 #define EBC_WAVE 64
 
@@ -14,6 +15,20 @@
         hipError_t _e = hipGetLastError();                   \
         if (_e != hipSuccess) return EBC_E_LAUNCH;           \
     } while (0)
+
+// The one dtype dispatch of the host launchers: runs the statements with E = the mfma.h element struct of the
+// runtime dtype code (EF32 / EF16 / EBF16) and T = E::T; an unknown code returns EBC_E_ARG from the enclosing
+// function.  Nests (the inner T / E shadow the outer: alias the outer ones first).  Per-dtype rules stay at the call
+// site, written on E::BYTES.
+#define EBC_DTYPE_CASE_(CODE, ELEM, ...) \
+    case CODE: { using E [[maybe_unused]] = ebc::ELEM; using T [[maybe_unused]] = E::T; __VA_ARGS__; } break;
+#define EBC_DTYPE_SWITCH(dtype, ...)                       \
+    switch (dtype) {                                       \
+        EBC_DTYPE_CASE_(EBC_F32, EF32, __VA_ARGS__)        \
+        EBC_DTYPE_CASE_(EBC_F16, EF16, __VA_ARGS__)        \
+        EBC_DTYPE_CASE_(EBC_BF16, EBF16, __VA_ARGS__)      \
+        default: return EBC_E_ARG;                         \
+    }
 
 namespace ebc {
 
@@ -63,16 +78,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp_mov<0xB1>(v));
-    v = fmaxf(v, dpp_mov<0x4E>(v));
-    v = fmaxf(v, dpp_mov<0x141>(v));
-    v = fmaxf(v, dpp_mov<0x140>(v));
-    v = fmaxf(v, dpp_rows<0x142, 0xA>(v, -INFINITY));
-    v = fmaxf(v, dpp_rows<0x143, 0xC>(v, -INFINITY));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
 __device__ __forceinline__ int wave_or(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
@@ -91,18 +96,6 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     return r;
 }
 
-__device__ __forceinline__ double block_sum_d(double v, double* scratch) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) scratch[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int i = 0; i < nw; ++i) r += scratch[i];
-    return r;
-}
-
 __device__ __forceinline__ int block_or(int v, int* scratch) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     v = wave_or(v);
@@ -115,15 +108,5 @@ __device__ __forceinline__ int block_or(int v, int* scratch) {
 }
 
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
-
-template <typename T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<__half>(__half v) { return __half2float(v); }
-template <> __device__ __forceinline__ float to_f32<__hip_bfloat16>(__hip_bfloat16 v) { return __bfloat162float(v); }
-
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half(v); }
-template <> __device__ __forceinline__ __hip_bfloat16 from_f32<__hip_bfloat16>(float v) { return __float2bfloat16(v); }
 
 }  // namespace ebc

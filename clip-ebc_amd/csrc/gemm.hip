@@ -20,6 +20,7 @@
 #include "ebc_common.h"
 #include "mfma.h"
 #include "kernels.h"
+#include "vec_io.h"
 
 using namespace ebc;
 
@@ -164,86 +165,34 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
     }
 }
 
-// output stores (default cache policy: r02 measured nt operand loads 25-35 % slower, nt stores no faster)
-template <class V> __device__ __forceinline__ void st_out(V* p, const V& v) { *p = v; }
-template <class TO> __device__ __forceinline__ void store4(TO* p, const float* v);
-template <> __device__ __forceinline__ void store4<float>(float* p, const float* v) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    st_out(reinterpret_cast<f4*>(p), f4{v[0], v[1], v[2], v[3]});
-}
-template <> __device__ __forceinline__ void store4<_Float16>(_Float16* p, const float* v) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 r = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-    st_out(reinterpret_cast<h4*>(p), r);
-}
-template <> __device__ __forceinline__ void store4<__bf16>(__bf16* p, const float* v) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    b4 r = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    st_out(reinterpret_cast<b4*>(p), r);
-}
-template <class T> __device__ __forceinline__ void load4(const T* p, float* v) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)p[i];
-}
-template <> __device__ __forceinline__ void load4<float>(const float* p, float* v) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+// 8 f32 as two 16-B accesses (vec_io.h's ld8 / st8 take f32 as one 32-B access; the epilogue's f32 rows and per-column
+// vectors are 16-B aligned): here and in pstore
+__device__ __forceinline__ void ld8f(const float* p, float* v) {
+    ld4(p, v);
+    ld4(p + 4, v + 4);
 }
 
-// 8 consecutive elements <-> float[8] (16 B for 16-bit types, 32 B for f32)
-template <class TO> __device__ __forceinline__ void store8(TO* p, const float* v) {
-    store4<TO>(p, v);
-    store4<TO>(p + 4, v + 4);
-}
-template <> __device__ __forceinline__ void store8<_Float16>(_Float16* p, const float* v) {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    h8 r = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
-            (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
-    st_out(reinterpret_cast<h8*>(p), r);
-}
-template <> __device__ __forceinline__ void store8<__bf16>(__bf16* p, const float* v) {
-    typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-    b8 r = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3], (__bf16)v[4], (__bf16)v[5], (__bf16)v[6], (__bf16)v[7]};
-    st_out(reinterpret_cast<b8*>(p), r);
-}
-template <class T> __device__ __forceinline__ void load8f(const T* p, float* v) {
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const t8 x = *reinterpret_cast<const t8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)x[i];
-}
-template <> __device__ __forceinline__ void load8f<float>(const float* p, float* v) {
-    load4<float>(p, v);
-    load4<float>(p + 4, v + 4);
-}
-
-// Epilogue output stores with a cache-policy immediate.  STORE_POL != 0: buffer stores through a resource based at the
-// tile's first output row (wave-uniform; 32-bit offsets inside the tile's rows), 16 = sc1 (write-through at the XCD
-// L2), 2 = nt
-#ifndef EBC_GEMM_STORE_POL
-#define EBC_GEMM_STORE_POL 0
-#endif
-constexpr int STORE_POL = EBC_GEMM_STORE_POL;
-// ... of the 16-bit outputs (C and the compute-dtype copies xh)
-#ifndef EBC_GEMM_STORE_POL_H
-#define EBC_GEMM_STORE_POL_H EBC_GEMM_STORE_POL
-#endif
-constexpr int STORE_POL_H = EBC_GEMM_STORE_POL_H;
+// Epilogue output stores (default cache policy: r02 measured nt operand loads 25-35 % slower, nt stores no faster): W
+// elements at base[off], base at the tile's first output row (wave-uniform), off a 32-bit offset inside the tile's rows.
+// SC1: one buffer store with the sc1 policy (write-through at the XCD L2), for the aux operand only.
 // The MLP pre-activation the c_fc product saves for the backward (EPI_GELU / EPI_LN_GELU aux, 22.5 MB a layer at 16
 // crops) is read again only by the GELU' product a whole forward later: written through (sc1) it does not sit dirty in
 // the L2s at the launch's end, where a launch boundary pays ~B / 6 TB/s for B dirty bytes (MI355X_MICROARCH.md
 // "boundary"; tools/lab/gemm_tl_lab.hip: c_fc with every store sc1 29.0 -> 26.8 us).  Same-box bench A/B (r06c, 4
 // interleaved pairs): 3678 -> 3690 crops/s.  The f32 residual-stream outputs (RESID / LN_BWD C, read two or three
 // launches later) written through as well measured 3 % SLOWER (3579): their readers still found them in the L2s.
-#ifndef EBC_GEMM_AUX_POL
-#define EBC_GEMM_AUX_POL 16
-#endif
-constexpr int AUX_POL = EBC_GEMM_AUX_POL;
-template <class TO, int W, int POL = STORE_POL> __device__ __forceinline__ void pstore(TO* base, unsigned off, const float* v) {
+constexpr int POL_SC1 = 16;
+template <class TO, int W, bool SC1 = false> __device__ __forceinline__ void pstore(TO* base, unsigned off, const float* v) {
     static_assert(W == 4 || W == 8, "4 or 8 elements");
-    if constexpr (POL == 0) {
-        if constexpr (W == 8) store8<TO>(base + off, v);
-        else store4<TO>(base + off, v);
+    if constexpr (!SC1) {
+        if constexpr (W == 8 && sizeof(TO) == 4) {
+            st4(base + off, v);
+            st4(base + off + 4, v + 4);
+        } else if constexpr (W == 8) {
+            st8(base + off, v);
+        } else {
+            st4(base + off, v);
+        }
     } else {
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -251,17 +200,17 @@ template <class TO, int W, int POL = STORE_POL> __device__ __forceinline__ void 
         const unsigned bo = off * (unsigned)sizeof(TO);
         if constexpr (std::is_same<TO, float>::value) {
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]),
-                                                         __float_as_uint(v[3])}, rs, bo, 0, POL);
+                                                         __float_as_uint(v[3])}, rs, bo, 0, POL_SC1);
             if constexpr (W == 8)
                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]),
-                                                             __float_as_uint(v[7])}, rs, bo + 16, 0, POL);
+                                                             __float_as_uint(v[7])}, rs, bo + 16, 0, POL_SC1);
         } else {
             typedef TO tw __attribute__((ext_vector_type(W)));
             tw r;
 #pragma unroll
             for (int i = 0; i < W; ++i) r[i] = (TO)v[i];
-            if constexpr (W == 8) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, r), rs, bo, 0, POL);
-            else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, r), rs, bo, 0, POL);
+            if constexpr (W == 8) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, r), rs, bo, 0, POL_SC1);
+            else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, r), rs, bo, 0, POL_SC1);
         }
     }
 }
@@ -528,30 +477,21 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
             }
         const char* abase = smem + wm * WM * ROWB;
         const char* bbase = smem + (BM + wn * WN) * ROWB;
+        auto read_frag = [&](const char* rp, int kk) -> typename E::Frag {
+            if constexpr (EB == 2) {
+                return __builtin_bit_cast(typename E::Frag, *reinterpret_cast<const uint4*>(rp + loff[kk][0]));
+            } else {
+                const float4 x0 = *reinterpret_cast<const float4*>(rp + loff[kk][0]);
+                const float4 x1 = *reinterpret_cast<const float4*>(rp + loff[kk][EB == 2 ? 0 : 1]);
+                return typename E::Frag{x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+            }
+        };
         auto load_frags = [&](auto bufc, int kk, typename E::Frag (&af)[TM], typename E::Frag (&bf)[TN]) {
             constexpr int buf = decltype(bufc)::value;
 #pragma unroll
-            for (int a = 0; a < TM; ++a) {
-                const char* rp = abase + buf * STAGE + a * 16 * ROWB;
-                if constexpr (EB == 2) {
-                    af[a] = __builtin_bit_cast(typename E::Frag, *reinterpret_cast<const uint4*>(rp + loff[kk][0]));
-                } else {
-                    const float4 x0 = *reinterpret_cast<const float4*>(rp + loff[kk][0]);
-                    const float4 x1 = *reinterpret_cast<const float4*>(rp + loff[kk][EB == 2 ? 0 : 1]);
-                    af[a] = typename E::Frag{x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-                }
-            }
+            for (int a = 0; a < TM; ++a) af[a] = read_frag(abase + buf * STAGE + a * 16 * ROWB, kk);
 #pragma unroll
-            for (int b = 0; b < TN; ++b) {
-                const char* rp = bbase + buf * STAGE + b * 16 * ROWB;
-                if constexpr (EB == 2) {
-                    bf[b] = __builtin_bit_cast(typename E::Frag, *reinterpret_cast<const uint4*>(rp + loff[kk][0]));
-                } else {
-                    const float4 x0 = *reinterpret_cast<const float4*>(rp + loff[kk][0]);
-                    const float4 x1 = *reinterpret_cast<const float4*>(rp + loff[kk][EB == 2 ? 0 : 1]);
-                    bf[b] = typename E::Frag{x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-                }
-            }
+            for (int b = 0; b < TN; ++b) bf[b] = read_frag(bbase + buf * STAGE + b * 16 * ROWB, kk);
         };
         // tile next_kt landed (count the later tiles still in flight): the issuing wave's counted vmcnt
         auto wait_tile = [&](int next_kt, auto tailc) {
@@ -643,11 +583,8 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
         //    that leaves the NPF younger prefetch loads in flight (tile 1's wait, vmcnt(0), covers them);
         //  * 4-wave tiles without loader waves: ahead of the ring as before (later, every counted ring wait would have to
         //    count them).
-#ifndef EBC_GEMM_PREF_LATE
-#define EBC_GEMM_PREF_LATE 1
-#endif
-        constexpr bool LATE_G = EBC_GEMM_PREF_LATE && PREF_G && NLW == 0 && S == 2;
-        constexpr bool LATE_R = EBC_GEMM_PREF_LATE && PREF && NLW > 0;
+        constexpr bool LATE_G = PREF_G && NLW == 0 && S == 2;
+        constexpr bool LATE_R = PREF && NLW > 0;
         constexpr int NPF = (TM / 2) * (TN / 2) * (int)sizeof(gp8_t) / 16;   // 16-B loads of prefetch_g
         if constexpr (PREF_G && !LATE_G) prefetch_g();
         if constexpr (PREF && !LATE_R) prefetch_r();
@@ -912,11 +849,11 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
                 float bv[NP > 0 ? NP : 1][8], bo[4];
 #pragma unroll
                 for (int q = 0; q < NP; ++q) {
-                    if (g.bias) load8f<float>(g.bias + nb + q * 32 + fg * 8, bv[q]);
+                    if (g.bias) ld8f(g.bias + nb + q * 32 + fg * 8, bv[q]);
                     else for (int i = 0; i < 8; ++i) bv[q][i] = 0.f;
                 }
                 if constexpr (ODD) {
-                    if (g.bias) load4<float>(g.bias + nb + NP * 32 + fg * 4, bo);
+                    if (g.bias) ld4(g.bias + nb + NP * 32 + fg * 4, bo);
                     else for (int i = 0; i < 4; ++i) bo[i] = 0.f;
                 }
                 // the row's 4 lanes (lanes fr + 16 fg) meet by lane swaps (same bits on all four)
@@ -934,8 +871,8 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
                 float rsv[LN ? TM : 1], rsmuv[LN ? TM : 1];
                 if constexpr (LN) {
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) load8f<float>(g.lnw + nb + q * 32 + fg * 8, lw[q]);
-                    if constexpr (ODD) load4<float>(g.lnw + nb + NP * 32 + fg * 4, lwo);
+                    for (int q = 0; q < NP; ++q) ld8f(g.lnw + nb + q * 32 + fg * 8, lw[q]);
+                    if constexpr (ODD) ld4(g.lnw + nb + NP * 32 + fg * 4, lwo);
                     const char* st = smem + S * STAGE;
 #pragma unroll
                     for (int a = 0; a < TM; ++a) {
@@ -1003,15 +940,13 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
                 // RESID with rpart: the lane's partial sum / sum of squares of its row's output values
                 float rsum = 0.f, rsq = 0.f;
                 const size_t tb = (size_t)m0 * g.N;          // the tile's first output row (pstore bases)
-                auto put = [&](auto* base, size_t off, const float* v, int w, auto polc) {
+                auto put = [&](auto* base, size_t off, const float* v, int w, auto sc1) {
                     using TT = typename std::remove_pointer<decltype(base)>::type;
-                    constexpr int POL = std::is_same<TT, float>::value ? decltype(polc)::value
-                                        : (decltype(polc)::value == STORE_POL ? STORE_POL_H : decltype(polc)::value);
-                    if (w == 8) pstore<TT, 8, POL>(base + tb, (unsigned)(off - tb), v);
-                    else pstore<TT, 4, POL>(base + tb, (unsigned)(off - tb), v);
+                    if (w == 8) pstore<TT, 8, decltype(sc1)::value>(base + tb, (unsigned)(off - tb), v);
+                    else pstore<TT, 4, decltype(sc1)::value>(base + tb, (unsigned)(off - tb), v);
                 };
-                using PolC = std::integral_constant<int, STORE_POL>;
-                using PolA = std::integral_constant<int, AUX_POL>;
+                using PolC = std::false_type;
+                using PolA = std::true_type;             // the aux operand: written through
                 auto finish = [&](float* v, int w, const float* bias, const float* lwv, const auto& pre, size_t off,
                                   const auto& xs) {
                     if constexpr (LN) {
@@ -1198,7 +1133,7 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
                         v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
                     }
                     if constexpr (EPI == EPI_GELU) {
-                        if (g.aux) pstore<T, 8, AUX_POL>(reinterpret_cast<T*>(g.aux) + tb, (unsigned)(off - tb), v);
+                        if (g.aux) pstore<T, 8, true>(reinterpret_cast<T*>(g.aux) + tb, (unsigned)(off - tb), v);
 #pragma unroll
                         for (int i = 0; i < 8; ++i) v[i] = quick_gelu(v[i]);
                     } else if constexpr (EPI == EPI_GELU_BWD) {
@@ -1276,10 +1211,11 @@ int launch_gemm_k(const GemmArgs& g, hipStream_t st)
             return EBC_E_ARG;
     }
     const int nwg = g.sk_total ? g.sk_grid : tiles * g.splits;
-    const int pi = probe_on() ? probe_start(EBC_PROBE_GEMM, EPI, BM, BN, MODE, g.M, g.N, g.kalg ? g.kalg : g.K, st) : -1;
-    hipLaunchKernelGGL((gemm_nt_kernel<E, TO, EPI, BM, BN, S, WGM, WGN, ROWB, MODE, SPL, NLW>), dim3(nwg),
-                       dim3(64 * (WGM * WGN + NLW)), LDS, st, g);
-    probe_stop(pi, st);
+    {
+        const ProbeScope probe(EBC_PROBE_GEMM, EPI, BM, BN, MODE, g.M, g.N, g.kalg ? g.kalg : g.K, st);
+        hipLaunchKernelGGL((gemm_nt_kernel<E, TO, EPI, BM, BN, S, WGM, WGN, ROWB, MODE, SPL, NLW>), dim3(nwg),
+                           dim3(64 * (WGM * WGN + NLW)), LDS, st, g);
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
     }
@@ -1703,12 +1639,7 @@ int conv_gemm(int dtype, int mode, int epi, const void* A, const void* B, void* 
         const TileCfg* c = find_cfg(conv_cfg(dtype != EBC_F32, mode, M, N));
         if (stats_tiles) *stats_tiles = (M + c->bm - 1) / c->bm;
     }
-    switch (dtype) {
-        case EBC_F32: return dispatch_conv<EF32>(g, mode, epi, ws, wsb, st);
-        case EBC_F16: return dispatch_conv<EF16>(g, mode, epi, ws, wsb, st);
-        case EBC_BF16: return dispatch_conv<EBF16>(g, mode, epi, ws, wsb, st);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return dispatch_conv<E>(g, mode, epi, ws, wsb, st));
 }
 
 // the MODE 0 products never split K (see pick_cfg), so they take no workspace
@@ -1723,12 +1654,8 @@ int gemm_nt(int dtype, int epi, int out_f32, const void* A, const void* B, void*
     if (a_rpg < 0 || (a_rpg > 0 && (a_goff < 0 || a_goff + a_rpg > a_gstride || epi != EPI_STORE))) return EBC_E_ARG;
     GemmArgs g{A, B, C, bias, resid, aux, M, N, K};
     g.a_rpg = a_rpg; g.a_gstride = a_gstride; g.a_goff = a_goff;
-    switch (dtype) {
-        case EBC_F32: return dispatch_epi<EF32>(g, epi, 0, st);   // element type is already f32
-        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, st);
-        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, st);
-    }
-    return EBC_E_ARG;
+    // f32: the element type is already f32 (out_f32 ignored)
+    EBC_DTYPE_SWITCH(dtype, return dispatch_epi<E>(g, epi, E::BYTES == 4 ? 0 : out_f32, st));
 }
 
 bool gemm_ln_bwd_fold_pays(int dtype, int M, int N, int K)
@@ -1788,11 +1715,7 @@ int gemm_nt_ln(int dtype, int epi, int out_f32, const void* A, const void* B, vo
     } else {
         return EBC_E_ARG;
     }
-    switch (dtype) {
-        case EBC_F16: return dispatch_epi<EF16>(g, epi, out_f32, st);
-        case EBC_BF16: return dispatch_epi<EBF16>(g, epi, out_f32, st);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return dispatch_epi<E>(g, epi, out_f32, st));    // (16-bit: EBC_F32 is rejected above)
 }
 }  // namespace ebc
 
@@ -1870,12 +1793,7 @@ extern "C" int ebc_gemm_wgrad(int dtype, const void* A, const void* B, float* C,
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || K % bk || N % 64) return EBC_E_ARG;
     GemmArgs g{A, B, C, nullptr, nullptr, nullptr, M, N, K};
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: return wgrad_launch<EF32>(g, workspace, workspace_bytes, st);
-        case EBC_F16: return wgrad_launch<EF16>(g, workspace, workspace_bytes, st);
-        case EBC_BF16: return wgrad_launch<EBF16>(g, workspace, workspace_bytes, st);
-    }
-    return EBC_E_ARG;
+    EBC_DTYPE_SWITCH(dtype, return wgrad_launch<E>(g, workspace, workspace_bytes, st));
 }
 
 extern "C" int ebc_transpose(int dtype, const void* in, void* out, int R, int C, long ld_out, ebc_stream_t stream)
@@ -1883,12 +1801,7 @@ extern "C" int ebc_transpose(int dtype, const void* in, void* out, int R, int C,
     if (!in || !out || R <= 0 || C <= 0 || C % 8 || ld_out < R || ld_out % 8) return EBC_E_ARG;
     const dim3 grid((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64));
     const hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL(transpose_kernel<float>, grid, dim3(256), 0, st, (const float*)in, (float*)out, R, C, ld_out); break;
-        case EBC_F16: hipLaunchKernelGGL(transpose_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)in, (_Float16*)out, R, C, ld_out); break;
-        case EBC_BF16: hipLaunchKernelGGL(transpose_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)in, (__bf16*)out, R, C, ld_out); break;
-        default: return EBC_E_ARG;
-    }
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL(transpose_kernel<T>, grid, dim3(256), 0, st, (const T*)in, (T*)out, R, C, ld_out));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }

@@ -19,6 +19,16 @@ bool touch_enabled();
 bool probe_on();
 int probe_start(int kind, int epi, int bm, int bn, int mode, int m, int n, int k, hipStream_t st);
 void probe_stop(int idx, hipStream_t st);
+// one launch's record: started here when the probe is armed, stopped where the scope ends
+struct ProbeScope {
+    const int idx;
+    const hipStream_t st;
+    ProbeScope(int kind, int epi, int bm, int bn, int mode, int m, int n, int k, hipStream_t s)
+        : idx(probe_on() ? probe_start(kind, epi, bm, bn, mode, m, n, k, s) : -1), st(s) {}
+    ~ProbeScope() { probe_stop(idx, st); }
+    ProbeScope(const ProbeScope&) = delete;
+    ProbeScope& operator=(const ProbeScope&) = delete;
+};
 // C[M,N] = A[M,K] . B[N,K]^T with a fused epilogue (include/ebc_hip.h ebc_gemm).  a_rpg > 0 (EPI_STORE only) maps the A
 // rows: output row r reads A row (r / a_rpg) * a_gstride + a_goff + r % a_rpg, i.e. a_rpg rows from offset a_goff of
 // every group of a_gstride rows (layer 0's prompt rows of each crop)
@@ -87,7 +97,7 @@ int layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int rpg
 int im2col(int dtype, const float* x, void* out, int B, int H, int W, int P, hipStream_t st);
 int embed_tokens(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta,
                  const float* vpt, long vpt_bstride, float* X, int B, int L, int G, int NVPT, int D, hipStream_t st);
-// ln_1 with the deep-VPT rows taken from the prompt (and written into X): replaces insert_vpt + layernorm_fwd
+// ln_1 with the deep-VPT rows taken from the prompt (and written into X) for the residual path
 int layernorm_fwd_vpt(int dtype, float* X, const float* vpt, long vpt_bstride, int L, int NVPT, const float* gamma,
                       const float* beta, void* out, float* mean, float* rstd, int M, int D, hipStream_t st);
 // ln_1 backward that routes the prompt rows' gradient to vpt_rows [B][NVPT][D] (and zeroes them in dx_out /
@@ -97,7 +107,6 @@ int layernorm_bwd_vpt(int dtype, const void* dy, const float* x, const float* me
                       const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, int D, float* vpt_rows,
                       int L, int NVPT, hipStream_t st);
 int vpt_sum(const float* rows, float* const* dst, int layers, int B, int NVPT, int D, hipStream_t st);
-int insert_vpt(float* X, const float* vpt, long vpt_bstride, int B, int L, int NVPT, int D, hipStream_t st);
 int vpt_grad(int dtype, float* dX, void* dXt, float* dvpt, int B, int L, int NVPT, int D, int per_batch, int accumulate,
              hipStream_t st);
 int head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
@@ -107,7 +116,6 @@ size_t head_bwd_ws_bytes(int P, int embed);
 int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const float* logit_scale, const float* anchors,
              const float* dlogits, const float* dexp, const float* gscale, void* dZ, float* dbias, float* dscale,
              int P, int HW, int NB, int embed, void* ws, size_t wsb, hipStream_t st);
-int attn_delta(int dtype, const void* dO, const void* O, float* delta, int B, int L, int H, hipStream_t st);
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st);
 int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, hipStream_t st,
                   const TouchList* touch = nullptr);

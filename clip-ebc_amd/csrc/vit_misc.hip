@@ -1,6 +1,6 @@
 // Memory-bound pieces of the CLIP-EBC ViT path on gfx950: LayerNorm fwd/bwd, patch im2col,
-// token embedding (+CLS, +pos, ln_pre, VPT rows), VPT insert / gradient, the blockwise
-// image-text similarity head fwd/bwd, and the attention-backward row statistic.
+// token embedding (+CLS, +pos, ln_pre, VPT rows), VPT gradient, and the blockwise
+// image-text similarity head fwd/bwd.
 //
 // Reference: LayerNorm (fp32 math)        models/clip/_clip/blocks.py:8-14
 //            token prologue               models/clip/model.py:147-158, image_encoder.py:141-148
@@ -13,37 +13,13 @@
 #include "kernels.h"
 #include "mfma.h"
 #include "touch.h"
+#include "vec_io.h"
 
 using namespace ebc;
 
 namespace {
 
 constexpr float LN_EPS = 1e-5f;
-
-template <class T> __device__ __forceinline__ void st4(T* p, float4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, float4 v) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<h4*>(p) = h4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-}
-template <> __device__ __forceinline__ void st4<__bf16>(__bf16* p, float4 v) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<b4*>(p) = b4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-}
-template <class T> __device__ __forceinline__ float4 ld4(const T* p) {
-    return make_float4((float)p[0], (float)p[1], (float)p[2], (float)p[3]);
-}
-template <> __device__ __forceinline__ float4 ld4<float>(const float* p) { return *reinterpret_cast<const float4*>(p); }
-template <> __device__ __forceinline__ float4 ld4<_Float16>(const _Float16* p) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    const h4 v = *reinterpret_cast<const h4*>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
-template <> __device__ __forceinline__ float4 ld4<__bf16>(const __bf16* p) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-    const b4 v = *reinterpret_cast<const b4*>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
 
 struct RowMap {            // out row r -> source row (r / rpg) * gstride + goff + r % rpg
     int rpg, gstride, goff;
@@ -300,17 +276,6 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ pa
     ln_row<NV>(v, gb, mean, rstd);
 #pragma unroll
     for (int i = 0; i < NV; ++i) *reinterpret_cast<float4*>(xo + 4 * lane + 256 * i) = v[i];
-}
-
-__global__ void insert_vpt_kernel(float* X, const float* vpt, long vpt_bstride, int B, int L, int NVPT, int D)
-{
-    const size_t total = (size_t)B * NVPT * D / 4;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int c4 = (int)(e % (D / 4));
-        const int r = (int)((e / (D / 4)) % NVPT), b = (int)(e / ((size_t)(D / 4) * NVPT));
-        reinterpret_cast<float4*>(X + ((size_t)b * L + 1 + r) * D)[c4] =
-            reinterpret_cast<const float4*>(vpt + b * vpt_bstride + (size_t)r * D)[c4];
-    }
 }
 
 // dvpt[r, c] (+)= sum_b dX[b, 1+r, c]  (or per batch when per_batch), then zero those rows of dX / dXt.
@@ -582,26 +547,6 @@ __global__ __launch_bounds__(512) void head_bias_finalize_kernel(const float* __
     }
 }
 
-// delta[b, h, q] = sum_d dO[b*L+q, h*64+d] * O[b*L+q, h*64+d]   (FA-style backward row statistic)
-template <class T>
-__global__ void attn_delta_kernel(const T* dO, const T* O, float* delta, int B, int L, int H)
-{
-    const int total = B * L * H;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-        const int h = e % H, row = e / H;
-        const int b = row / L, q = row % L;
-        const T* a = dO + (size_t)row * H * 64 + h * 64;
-        const T* o = O + (size_t)row * H * 64 + h * 64;
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 64; d += 4) {
-            const float4 x = ld4<T>(a + d), y = ld4<T>(o + d);
-            s += (x.x * y.x + x.y * y.y) + (x.z * y.z + x.w * y.w);
-        }
-        delta[((size_t)b * H + h) * L + q] = s;
-    }
-}
-
 template <class T>
 __global__ void cast_kernel(const float* in, T* out, size_t n4)
 {
@@ -623,14 +568,9 @@ static int ln_fwd_launch(int dtype, const float* x, RowMap map, const float* gam
                          float* outf, float* mean, float* rstd, int M, VptIns vi, hipStream_t st)
 {
     const dim3 grid((M + 3) / 4);
-    const int pi = probe_on() ? probe_start(EBC_PROBE_LN_FWD, 0, 0, 0, 0, M, 768, 0, st) : -1;
-    struct Stop { int i; hipStream_t s; ~Stop() { probe_stop(i, s); } } stop{pi, st};
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL((ln_fwd_kernel<float, 3>), grid, dim3(256), 0, st, x, map, gamma, beta, (float*)out, outf, mean, rstd, M, vi); break;
-        case EBC_F16: hipLaunchKernelGGL((ln_fwd_kernel<_Float16, 3>), grid, dim3(256), 0, st, x, map, gamma, beta, (_Float16*)out, outf, mean, rstd, M, vi); break;
-        case EBC_BF16: hipLaunchKernelGGL((ln_fwd_kernel<__bf16, 3>), grid, dim3(256), 0, st, x, map, gamma, beta, (__bf16*)out, outf, mean, rstd, M, vi); break;
-        default: return EBC_E_ARG;
-    }
+    const ProbeScope probe(EBC_PROBE_LN_FWD, 0, 0, 0, 0, M, 768, 0, st);
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_fwd_kernel<T, 3>), grid, dim3(256), 0, st, x, map, gamma, beta, (T*)out,
+                                               outf, mean, rstd, M, vi));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -657,8 +597,7 @@ static int ln_bwd_t(int dy_f32, const void* dy, const float* x, RowMap map, cons
                     const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, VptOut vo, hipStream_t st)
 {
     const dim3 grid((M + 3) / 4);
-    const int pi = probe_on() ? probe_start(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 768, 0, st) : -1;
-    struct Stop { int i; hipStream_t s; ~Stop() { probe_stop(i, s); } } stop{pi, st};
+    const ProbeScope probe(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 768, 0, st);
     if (dy_f32)
         hipLaunchKernelGGL((ln_bwd_kernel<T, float, 3>), grid, dim3(256), 0, st, (const float*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (T*)dx_out_t, M, vo, TouchList{});
     else
@@ -682,17 +621,11 @@ int layernorm_bwd_fill(int dtype, const float* dy, const float* x, int rpg, int 
     const int Mf = M / rpg * gstride;
     const dim3 grid((Mf + 3) / 4);
     if (lines > (size_t)grid.x * 256) t = TouchList{};
-    const int pi = probe_on() ? probe_start(EBC_PROBE_LN_BWD, 0, 0, 0, 0, Mf, 768, 0, st) : -1;
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL((ln_bwd_kernel<float, float, 3, true>), grid, dim3(256), 0, st, dy, x, map, mean, rstd,
-                                         gamma, nullptr, dx_out, (float*)dx_out_t, Mf, vo, t); break;
-        case EBC_F16: hipLaunchKernelGGL((ln_bwd_kernel<_Float16, float, 3, true>), grid, dim3(256), 0, st, dy, x, map, mean,
-                                         rstd, gamma, nullptr, dx_out, (_Float16*)dx_out_t, Mf, vo, t); break;
-        case EBC_BF16: hipLaunchKernelGGL((ln_bwd_kernel<__bf16, float, 3, true>), grid, dim3(256), 0, st, dy, x, map, mean,
-                                          rstd, gamma, nullptr, dx_out, (__bf16*)dx_out_t, Mf, vo, t); break;
-        default: probe_stop(pi, st); return EBC_E_ARG;
+    {
+        const ProbeScope probe(EBC_PROBE_LN_BWD, 0, 0, 0, 0, Mf, 768, 0, st);
+        EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_bwd_kernel<T, float, 3, true>), grid, dim3(256), 0, st, dy, x, map,
+                                                   mean, rstd, gamma, nullptr, dx_out, (T*)dx_out_t, Mf, vo, t));
     }
-    probe_stop(pi, st);
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -704,12 +637,9 @@ int layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int rpg
     if (D != 768 || M <= 0) return EBC_E_UNSUPPORTED;
     const RowMap map{rpg > 0 ? rpg : M, gstride, goff};
     const VptOut vo{nullptr, 1, 0};
-    switch (dtype) {
-        case EBC_F32: return ln_bwd_t<float>(1, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-        case EBC_F16: return ln_bwd_t<_Float16>(dy_f32, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-        case EBC_BF16: return ln_bwd_t<__bf16>(dy_f32, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-    }
-    return EBC_E_ARG;
+    // f32: dy is always f32
+    EBC_DTYPE_SWITCH(dtype, return ln_bwd_t<T>(E::BYTES == 4 ? 1 : dy_f32, dy, x, map, mean, rstd, gamma, dx_in, dx_out,
+                                               dx_out_t, M, vo, st));
 }
 
 int im2col(int dtype, const float* x, void* out, int B, int H, int W, int P, hipStream_t st)
@@ -719,12 +649,7 @@ int im2col(int dtype, const float* x, void* out, int B, int H, int W, int P, hip
     const int k4 = 3 * P * P / 4, blk = (k4 + 63) / 64 * 64;
     if (rows <= 0 || rows > INT_MAX || blk > 1024 || (size_t)B * 3 * H * W > (size_t)INT_MAX * 4) return EBC_E_ARG;
     const dim3 grid((unsigned)rows);
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL(im2col_kernel<float>, grid, dim3(blk), 0, st, x, (float*)out, H, W, P); break;
-        case EBC_F16: hipLaunchKernelGGL(im2col_kernel<_Float16>, grid, dim3(blk), 0, st, x, (_Float16*)out, H, W, P); break;
-        case EBC_BF16: hipLaunchKernelGGL(im2col_kernel<__bf16>, grid, dim3(blk), 0, st, x, (__bf16*)out, H, W, P); break;
-        default: return EBC_E_ARG;
-    }
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL(im2col_kernel<T>, grid, dim3(blk), 0, st, x, (T*)out, H, W, P));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -746,12 +671,8 @@ int layernorm_bwd_vpt(int dtype, const void* dy, const float* x, const float* me
     if (D != 768 || M <= 0 || M % L || NVPT < 1 || NVPT >= L || !vpt_rows) return EBC_E_UNSUPPORTED;
     const RowMap map{M, 0, 0};
     const VptOut vo{vpt_rows, L, NVPT};
-    switch (dtype) {
-        case EBC_F32: return ln_bwd_t<float>(1, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-        case EBC_F16: return ln_bwd_t<_Float16>(0, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-        case EBC_BF16: return ln_bwd_t<__bf16>(0, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st);
-    }
-    return EBC_E_ARG;
+    // dy in the compute dtype (f32: dy_f32 = 1)
+    EBC_DTYPE_SWITCH(dtype, return ln_bwd_t<T>(E::BYTES == 4, dy, x, map, mean, rstd, gamma, dx_in, dx_out, dx_out_t, M, vo, st));
 }
 
 int layernorm_bwd_rows(int dtype, const void* dy, const float* x, int rpg, int gstride, int goff, const float* mean,
@@ -762,17 +683,9 @@ int layernorm_bwd_rows(int dtype, const void* dy, const float* x, int rpg, int g
     const RowMap map{rpg, gstride, goff};
     const VptOut vo{nullptr, 1, 0};
     const dim3 grid((M + 3) / 4);
-    const int pi = probe_on() ? probe_start(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 768, 0, st) : -1;
-    struct Stop { int i; hipStream_t s; ~Stop() { probe_stop(i, s); } } stop{pi, st};
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL((ln_bwd_kernel<float, float, 3, false, true>), grid, dim3(256), 0, st, (const float*)dy,
-                                         x, map, mean, rstd, gamma, dx_in, dx_out, (float*)nullptr, M, vo, TouchList{}); break;
-        case EBC_F16: hipLaunchKernelGGL((ln_bwd_kernel<_Float16, _Float16, 3, false, true>), grid, dim3(256), 0, st,
-                                         (const _Float16*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (_Float16*)nullptr, M, vo, TouchList{}); break;
-        case EBC_BF16: hipLaunchKernelGGL((ln_bwd_kernel<__bf16, __bf16, 3, false, true>), grid, dim3(256), 0, st,
-                                          (const __bf16*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (__bf16*)nullptr, M, vo, TouchList{}); break;
-        default: return EBC_E_ARG;
-    }
+    const ProbeScope probe(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 768, 0, st);
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_bwd_kernel<T, T, 3, false, true>), grid, dim3(256), 0, st, (const T*)dy, x,
+                                               map, mean, rstd, gamma, dx_in, dx_out, (T*)nullptr, M, vo, TouchList{}));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -790,24 +703,12 @@ int vpt_sum(const float* rows, float* const* dst, int layers, int B, int NVPT, i
     return EBC_OK;
 }
 
-int insert_vpt(float* X, const float* vpt, long vpt_bstride, int B, int L, int NVPT, int D, hipStream_t st)
-{
-    const size_t n = (size_t)B * NVPT * D / 4;
-    hipLaunchKernelGGL(insert_vpt_kernel, dim3(grid_for(n)), dim3(256), 0, st, X, vpt, vpt_bstride, B, L, NVPT, D);
-    EBC_CHECK_LAUNCH();
-    return EBC_OK;
-}
-
 int vpt_grad(int dtype, float* dX, void* dXt, float* dvpt, int B, int L, int NVPT, int D, int per_batch, int accumulate, hipStream_t st)
 {
     if (D % 256 || NVPT <= 0 || B <= 0) return NVPT == 0 ? EBC_OK : EBC_E_UNSUPPORTED;
     const dim3 grid((unsigned)(NVPT * (D / 256)));
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL(vpt_grad_kernel<float>, grid, dim3(256), 0, st, dX, (float*)dXt, dvpt, B, L, NVPT, D, per_batch, accumulate); break;
-        case EBC_F16: hipLaunchKernelGGL(vpt_grad_kernel<_Float16>, grid, dim3(256), 0, st, dX, (_Float16*)dXt, dvpt, B, L, NVPT, D, per_batch, accumulate); break;
-        case EBC_BF16: hipLaunchKernelGGL(vpt_grad_kernel<__bf16>, grid, dim3(256), 0, st, dX, (__bf16*)dXt, dvpt, B, L, NVPT, D, per_batch, accumulate); break;
-        default: return EBC_E_ARG;
-    }
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL(vpt_grad_kernel<T>, grid, dim3(256), 0, st, dX, (T*)dXt, dvpt, B, L, NVPT, D,
+                                               per_batch, accumulate));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -818,12 +719,8 @@ static int head_fwd_t(int dtype_z, const void* Z, const float* text, const float
 {
     const dim3 grid((P + HEAD_FWD_PPB - 1) / HEAD_FWD_PPB);
     const size_t lds = (size_t)NB * CH * 4;
-    switch (dtype_z) {
-        case EBC_F32: hipLaunchKernelGGL((head_fwd_kernel<float, CH>), grid, dim3(256), lds, st, (const float*)Z, text, logit_scale, anchors, logits, expo, P, HW, NB); break;
-        case EBC_F16: hipLaunchKernelGGL((head_fwd_kernel<_Float16, CH>), grid, dim3(256), lds, st, (const _Float16*)Z, text, logit_scale, anchors, logits, expo, P, HW, NB); break;
-        case EBC_BF16: hipLaunchKernelGGL((head_fwd_kernel<__bf16, CH>), grid, dim3(256), lds, st, (const __bf16*)Z, text, logit_scale, anchors, logits, expo, P, HW, NB); break;
-        default: return EBC_E_ARG;
-    }
+    EBC_DTYPE_SWITCH(dtype_z, hipLaunchKernelGGL((head_fwd_kernel<T, CH>), grid, dim3(256), lds, st, (const T*)Z, text,
+                                                 logit_scale, anchors, logits, expo, P, HW, NB));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -849,24 +746,11 @@ static int head_bwd_t(int dtype_z, int dtype_dz, const void* Z, const float* tex
     const dim3 grid(nblk);
     const size_t lds = ((size_t)NB * CH + 4 * CH + 4) * 4;
     constexpr int LDS_MAX = (16 * CH + 4 * CH + 4) * 4;      // NB <= 16 (embed 1024: 81 KiB)
-#define HB(TZ, TD) if (!ensure_lds<head_bwd_kernel<TZ, TD, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH; \
-    hipLaunchKernelGGL((head_bwd_kernel<TZ, TD, CH>), grid, dim3(256), lds, st, (const TZ*)Z, text, logit_scale, anchors, dlogits, dexp, gscale, (TD*)dZ, part, P, HW, NB)
     // the dZ element type is the caller's buffer type (dtype_dz), independent of Z's
-#define HBZ(TZ)                                                   \
-    switch (dtype_dz) {                                           \
-        case EBC_F32: HB(TZ, float); break;                       \
-        case EBC_F16: HB(TZ, _Float16); break;                    \
-        case EBC_BF16: HB(TZ, __bf16); break;                     \
-        default: return EBC_E_ARG;                                \
-    }
-    switch (dtype_z) {
-        case EBC_F32: HBZ(float); break;
-        case EBC_F16: HBZ(_Float16); break;
-        case EBC_BF16: HBZ(__bf16); break;
-        default: return EBC_E_ARG;
-    }
-#undef HBZ
-#undef HB
+    EBC_DTYPE_SWITCH(dtype_z, using TZ = T; EBC_DTYPE_SWITCH(dtype_dz,
+        if (!ensure_lds<head_bwd_kernel<TZ, T, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH;
+        hipLaunchKernelGGL((head_bwd_kernel<TZ, T, CH>), grid, dim3(256), lds, st, (const TZ*)Z, text, logit_scale, anchors,
+                           dlogits, dexp, gscale, (T*)dZ, part, P, HW, NB)));
     EBC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(head_bias_finalize_kernel<CH>, dim3(CH / 64 + 1), dim3(512), 0, st, part, nblk, dbias, dscale);
@@ -894,28 +778,10 @@ int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const 
     return EBC_E_UNSUPPORTED;
 }
 
-int attn_delta(int dtype, const void* dO, const void* O, float* delta, int B, int L, int H, hipStream_t st)
-{
-    const int n = B * L * H;
-    switch (dtype) {
-        case EBC_F32: hipLaunchKernelGGL(attn_delta_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)dO, (const float*)O, delta, B, L, H); break;
-        case EBC_F16: hipLaunchKernelGGL(attn_delta_kernel<_Float16>, dim3(grid_for(n)), dim3(256), 0, st, (const _Float16*)dO, (const _Float16*)O, delta, B, L, H); break;
-        case EBC_BF16: hipLaunchKernelGGL(attn_delta_kernel<__bf16>, dim3(grid_for(n)), dim3(256), 0, st, (const __bf16*)dO, (const __bf16*)O, delta, B, L, H); break;
-        default: return EBC_E_ARG;
-    }
-    EBC_CHECK_LAUNCH();
-    return EBC_OK;
-}
-
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st)
 {
     if (n % 4) return EBC_E_ARG;
-    switch (dtype) {
-        case EBC_F16: hipLaunchKernelGGL(cast_kernel<_Float16>, dim3(grid_for(n / 4)), dim3(256), 0, st, in, (_Float16*)out, n / 4); break;
-        case EBC_BF16: hipLaunchKernelGGL(cast_kernel<__bf16>, dim3(grid_for(n / 4)), dim3(256), 0, st, in, (__bf16*)out, n / 4); break;
-        case EBC_F32: hipLaunchKernelGGL(cast_kernel<float>, dim3(grid_for(n / 4)), dim3(256), 0, st, in, (float*)out, n / 4); break;
-        default: return EBC_E_ARG;
-    }
+    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL(cast_kernel<T>, dim3(grid_for(n / 4)), dim3(256), 0, st, in, (T*)out, n / 4));
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }

@@ -67,24 +67,26 @@ _X = 0x1000          # a non-NULL pointer value; every call below is rejected be
 F32, F16 = 0, 1
 
 
-def _ln_fwd(lib, x=_X, rpg=0, gs=0, go=0, gamma=_X, beta=_X, out=_X, outf=None, mean=_X, rstd=_X, M=8):
-    return lib.ebc_layernorm_fwd(F16, x, rpg, gs, go, gamma, beta, out, outf, mean, rstd, M, 768, None)
+def _ln_fwd(lib, x=_X, rpg=0, gs=0, go=0, gamma=_X, beta=_X, out=_X, outf=None, mean=_X, rstd=_X, M=8, dtype=F16):
+    return lib.ebc_layernorm_fwd(dtype, x, rpg, gs, go, gamma, beta, out, outf, mean, rstd, M, 768, None)
 
 
-def _ln_bwd(lib, dy=_X, x=_X, rpg=0, gs=0, go=0, mean=_X, rstd=_X, gamma=_X, dx_in=None, dx_out=_X, dxt=None, M=8):
-    return lib.ebc_layernorm_bwd(F16, 0, dy, x, rpg, gs, go, mean, rstd, gamma, dx_in, dx_out, dxt, M, 768, None)
+def _ln_bwd(lib, dy=_X, x=_X, rpg=0, gs=0, go=0, mean=_X, rstd=_X, gamma=_X, dx_in=None, dx_out=_X, dxt=None, M=8,
+            dtype=F16):
+    return lib.ebc_layernorm_bwd(dtype, 0, dy, x, rpg, gs, go, mean, rstd, gamma, dx_in, dx_out, dxt, M, 768, None)
 
 
 @pytest.mark.parametrize("kw", [dict(x=None), dict(gamma=None), dict(beta=None), dict(out=None, outf=None),
                                 dict(rstd=None), dict(rpg=4, gs=7, go=-1), dict(rpg=4, gs=7, go=4),
-                                dict(rpg=196, gs=229, go=34), dict(rpg=1, gs=0, go=0)])
+                                dict(rpg=196, gs=229, go=34), dict(rpg=1, gs=0, go=0), dict(dtype=3)])
 def test_layernorm_fwd_rejects_without_device(lib, kw):
-    """NULL x / gamma / beta, no output at all, mean without rstd, a row map that leaves its group."""
+    """NULL x / gamma / beta, no output at all, mean without rstd, a row map that leaves its group, a dtype that is
+    none of the three."""
     assert _ln_fwd(lib, **kw) == EBC_E_ARG
 
 
 @pytest.mark.parametrize("kw", [dict(dy=None), dict(x=None), dict(mean=None), dict(rstd=None), dict(gamma=None),
-                                dict(dx_out=None), dict(rpg=4, gs=7, go=-1), dict(rpg=49, gs=82, go=34)])
+                                dict(dx_out=None), dict(rpg=4, gs=7, go=-1), dict(rpg=49, gs=82, go=34), dict(dtype=3)])
 def test_layernorm_bwd_rejects_without_device(lib, kw):
     assert _ln_bwd(lib, **kw) == EBC_E_ARG
 
@@ -102,20 +104,24 @@ def test_attention_rejects_without_device(lib):
                 assert lib.ebc_attention_bwd(dt, *a, 1, L, 2, None) == EBC_E_ARG, (dt, L, bad)
     for dt, L in ((0, 5), (0, 200), (0, 300), (1, 300), (2, 257)):
         assert lib.ebc_attention_bwd(dt, _X, _X, _X, _X, None, _X, 1, L, 2, None) == EBC_E_ARG, (dt, L)
+    for L in (5, 229, 300):                  # a dtype that is none of the three, on the resident and the streamed path
+        assert lib.ebc_attention_fwd(3, _X, _X, _X, 1, L, 2, None) == EBC_E_ARG
+        assert lib.ebc_attention_bwd(3, _X, _X, _X, _X, _X, _X, 1, L, 2, None) == EBC_E_ARG
 
 
-def _head_fwd(lib, Z=_X, text=_X, ls=_X, anchors=_X, logits=_X, expo=_X, P=8, HW=4):
-    return lib.ebc_head_fwd(F32, Z, text, ls, anchors, logits, expo, P, HW, 5, 512, None)
+def _head_fwd(lib, Z=_X, text=_X, ls=_X, anchors=_X, logits=_X, expo=_X, P=8, HW=4, dtype=F32):
+    return lib.ebc_head_fwd(dtype, Z, text, ls, anchors, logits, expo, P, HW, 5, 512, None)
 
 
-def _head_bwd(lib, Z=_X, text=_X, ls=_X, anchors=_X, dl=_X, de=_X, dZ=_X, P=8, HW=4):
-    return lib.ebc_head_bwd(F32, F32, Z, text, ls, anchors, dl, de, None, dZ, None, None, P, HW, 5, 512, None, 0, None)
+def _head_bwd(lib, Z=_X, text=_X, ls=_X, anchors=_X, dl=_X, de=_X, dZ=_X, P=8, HW=4, dtype=F32, dtype_dz=F32):
+    return lib.ebc_head_bwd(dtype, dtype_dz, Z, text, ls, anchors, dl, de, None, dZ, None, None, P, HW, 5, 512, None, 0, None)
 
 
 @pytest.mark.parametrize("kw", [dict(P=0), dict(P=-4), dict(HW=0), dict(HW=-1), dict(P=8, HW=3), dict(Z=None),
-                                dict(text=None), dict(ls=None), dict(anchors=None)])
+                                dict(text=None), dict(ls=None), dict(anchors=None), dict(dtype=3)])
 def test_head_rejects_without_device(lib, kw):
-    """P <= 0, HW <= 0 (p / HW on the device), P not a whole number of images, NULL operands."""
+    """P <= 0, HW <= 0 (p / HW on the device), P not a whole number of images, NULL operands, a dtype of Z that is none
+    of the three."""
     assert _head_fwd(lib, **kw) == EBC_E_ARG
     assert _head_bwd(lib, **kw) == EBC_E_ARG
 
@@ -124,10 +130,12 @@ def test_head_outputs_and_cast_reject_without_device(lib):
     assert _head_fwd(lib, logits=None) == EBC_E_ARG and _head_fwd(lib, expo=None) == EBC_E_ARG
     assert _head_bwd(lib, dl=None) == EBC_E_ARG and _head_bwd(lib, de=None) == EBC_E_ARG
     assert _head_bwd(lib, dZ=None) == EBC_E_ARG
+    assert _head_bwd(lib, dtype_dz=3) == EBC_E_ARG and _head_bwd(lib, dtype=F16, dtype_dz=3) == EBC_E_ARG
     # d bias / d logit_scale asked for without a workspace (already rejected before this change)
     assert lib.ebc_head_bwd(F32, F32, _X, _X, _X, _X, _X, _X, None, _X, _X, None, 8, 4, 5, 512, None, 0, None) == EBC_E_ARG
     assert lib.ebc_cast_f32(F16, None, _X, 8, None) == EBC_E_ARG
     assert lib.ebc_cast_f32(F16, _X, None, 8, None) == EBC_E_ARG
+    assert lib.ebc_cast_f32(3, _X, _X, 8, None) == EBC_E_ARG
 
 
 EBC_E_UNSUPPORTED = -3
@@ -171,7 +179,7 @@ def _rows(lib, dtype=F16, out_f32=0, A=_X, B=_X, C=_X, bias=None, M=15, N=768, K
 
 
 @pytest.mark.parametrize("kw", [dict(A=None), dict(B=None), dict(C=None), dict(K=800), dict(dtype=F32, K=48), dict(N=800),
-                                dict(M=0), dict(dtype=5), dict(rpg=-1), dict(go=-1), dict(go=19), dict(rpg=24),
+                                dict(M=0), dict(dtype=5), dict(dtype=3), dict(rpg=-1), dict(go=-1), dict(go=19), dict(rpg=24),
                                 dict(rpg=1, gs=0, go=0), dict(rpg=196, gs=229, go=34)])
 def test_gemm_rows_rejects_without_device(lib, kw):
     """ebc_gemm's checks, and a row map that leaves its group."""

@@ -19,6 +19,7 @@ namespace ebc {
 bool probe_on() { return false; }
 int probe_start(int, int, int, int, int, int, int, int, hipStream_t) { return -1; }
 void probe_stop(int, hipStream_t) {}
+bool touch_enabled() { return false; }
 }  // namespace ebc
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
