@@ -344,7 +344,13 @@ int ebc_conv3x3_fwd(int dtype, const void* xpad, const void* weight, void* out, 
  * G workgroups share the k-tiles of the tiles past the last whole wave of 256 (those run first as a plain
  * launch). Host-only. */
 int ebc_conv_tile_config(int dtype, int mode, int M, int N, int K, int* out);
-/* dw[N][C][3][3] f32 = weight gradient from dzT and xT3 */
+/* dw[N][C][3][3] f32 = weight gradient from dzT and xT3.
+ * Padding contract: the product runs over all Kq columns of dzT, and column b*HWp + r meets position
+ * b*Pimg + ky*W + r of xT3's rows, which for r >= H*W is the image's next rows (input data for ky < 2) and the
+ * zeros behind them.  So dzT's padding columns inside Kq -- r >= H*W of every image and the columns past B*HWp --
+ * MUST be zero (ebc_bn_bwd_apply writes them so); xT3 is taken as ebc_dec_transpose3 writes it, and the positions
+ * of its rows that belong to no image row (past (H+2)*W of an image, past the last image) meet only those zero
+ * columns, so their content does not reach dw as long as it is finite.  dzT's columns >= Kq are never read. */
 int ebc_conv3x3_wgrad(int dtype, const void* dzT, const void* xT3, float* dw, void* ws, size_t wsb, int B, int H,
                       int W, int C, int N, ebc_stream_t stream);
 /* BatchNorm2d statistics -> mean, rstd, scale = gamma*rstd, shift = beta - mean*scale; running stats
