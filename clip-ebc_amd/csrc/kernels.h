@@ -116,6 +116,12 @@ size_t head_bwd_ws_bytes(int P, int embed);
 int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const float* logit_scale, const float* anchors,
              const float* dlogits, const float* dexp, const float* gscale, void* dZ, float* dbias, float* dscale,
              int P, int HW, int NB, int embed, void* ws, size_t wsb, hipStream_t st);
+// d (logits, exp) / d text [NB][embed] (the raw rows, through the head's F.normalize): per-block partials in ws
+// (head_bwd_text_ws_bytes), summed in block order by a second launch
+size_t head_bwd_text_ws_bytes(int P, int NB, int embed);
+int head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                  const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                  int embed, void* ws, size_t wsb, hipStream_t st);
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st);
 int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, hipStream_t st,
                   const TouchList* touch = nullptr);

@@ -547,6 +547,185 @@ __global__ __launch_bounds__(512) void head_bias_finalize_kernel(const float* __
     }
 }
 
+// ---- d text (freeze_text_encoder=False, models/clip/model.py:201-208): the gradient of (logits, exp) with respect to
+// the RAW text rows, through the head's own F.normalize of them.  With dl[p][k] as head_bwd_kernel forms it,
+//   dtn_k = exp(ls) sum_p dl[p][k] zn_p,   <tn_k, dtn_k> = sum_p dl[p][k] logits[p][k]   (logits = exp(ls) <zn, tn>)
+//   dt_k  = (dtn_k - tn_k <tn_k, dtn_k>) / max(||t_k||, 1e-12)       (dtn_k / 1e-12 where the norm is clamped)
+// A kernel of its own that recomputes dl from Z (one more read of Z, which the frozen path never pays), so the
+// head_bwd_kernel instances stay as they are.  One wave per pixel as above, 64 pixels a workgroup (16 a wave, loaded
+// four -- two at 1024 channels -- at a time); a lane keeps sum_p dl[p][k] zn_p[c] for its NV channels of KB bins:
+// KB x NV = 128 accumulators at both widths (KB = 16 at 512 channels: one pass; KB = 8 at 1024: two passes over the
+// wave's pixels, the second with dl and 1 / ||z|| from LDS).  The four waves' sums meet in LDS in wave order, the
+// workgroup stores part[block] = [NB][CH] sums then 16 dot slots (plain stores), and head_text_finalize_kernel adds the
+// blocks in head_bias_finalize_kernel's fixed order: bit-reproducible, no float atomics.
+constexpr int HEAD_TXT_PPB = 64;
+
+template <int CH>
+constexpr int head_txt_kb() { return CH <= 512 ? 16 : 8; }
+
+// floats of one workgroup's partial: [NB][CH] sums, then the bins' dot slots padded to 16 (rows stay float4-aligned)
+__host__ __device__ inline size_t head_txt_stride(int NB, int CH) { return (size_t)NB * CH + 16; }
+
+template <class TZ, int CH>
+__global__ __launch_bounds__(256) void head_text_bwd_kernel(const TZ* __restrict__ Z, const float* text, const float* logit_scale,
+                                                            const float* anchors, const float* dlogits, const float* dexp,
+                                                            const float* gscale, float* __restrict__ part, int P, int HW, int NB)
+{
+    constexpr int NV = CH / 64, KB = head_txt_kb<CH>(), PPW = HEAD_TXT_PPB / 4, G = 32 / NV;
+    extern __shared__ __attribute__((aligned(16))) float tn[];
+    float* red = tn + NB * CH;              // [KB][CH]: the waves' sums, combined in wave order
+    float* dl_l = red + KB * CH;            // [4 waves][PPW][16]
+    float* inv_l = dl_l + 4 * PPW * 16;     // [4][PPW]
+    float* dot_l = inv_l + 4 * PPW;         // [4][16]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float s = expf(*logit_scale);
+    const float gs = gscale ? *gscale : 1.0f;
+    load_text<CH>(text, NB, tn);
+    float* pblk = part + (size_t)blockIdx.x * head_txt_stride(NB, CH);
+    float dots[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) dots[k] = 0.f;
+    for (int k0 = 0; k0 < NB; k0 += KB) {
+        float acc[KB][NV];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+            for (int j = 0; j < NV; ++j) acc[kk][j] = 0.f;
+        for (int i0 = 0; i0 < PPW; i0 += G) {
+            const int p0 = blockIdx.x * HEAD_TXT_PPB + w + 4 * i0;
+            if (p0 >= P) break;
+            float vv[G][NV];
+#pragma unroll
+            for (int g = 0; g < G; ++g) load_pix<TZ, CH>(Z + (size_t)min(p0 + 4 * g, P - 1) * CH, vv[g]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int p = p0 + 4 * g, i = i0 + g;
+                if (p >= P) continue;
+                float* v = vv[g];
+                float dlr[KB], inv;
+                if (KB >= 16 || k0 == 0) {
+                    float ss = 0.f;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) ss += v[j] * v[j];
+                    inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+                    float zs[NV];
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) zs[j] = s * (v[j] * inv);
+                    float lg[16], pr[16];
+                    float mx = -INFINITY;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        lg[k] = k < NB ? wave_sum(text_dot<CH>(tn + k * CH, zs)) : -INFINITY;
+                        mx = fmaxf(mx, lg[k]);
+                    }
+                    float se = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) { pr[k] = k < NB ? expf(lg[k] - mx) : 0.f; if (k < NB) se += pr[k]; }
+                    float e = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) if (k < NB) { pr[k] /= se; e += pr[k] * anchors[k]; }
+                    const int b = p / HW, hw = p % HW;
+                    const float de = dexp[(size_t)b * HW + hw] * gs;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        if (k >= NB) continue;
+                        // d logit_k, as in head_bwd_kernel
+                        const float dl = dlogits[((size_t)b * NB + k) * HW + hw] * gs + de * pr[k] * (anchors[k] - e);
+                        dots[k] += dl * lg[k];
+                        if (k < KB) dlr[k % KB] = dl;
+                        if (KB < 16 && lane == 0) dl_l[(w * PPW + i) * 16 + k] = dl;
+                    }
+                    if (KB < 16 && lane == 0) inv_l[w * PPW + i] = inv;
+                } else {
+                    inv = inv_l[w * PPW + i];
+#pragma unroll
+                    for (int kk = 0; kk < KB; ++kk) dlr[kk] = k0 + kk < NB ? dl_l[(w * PPW + i) * 16 + k0 + kk] : 0.f;
+                }
+                float zn[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) zn[j] = v[j] * inv;
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) {
+                    if (k0 + kk >= NB) continue;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) acc[kk][j] += dlr[kk] * zn[j];
+                }
+            }
+        }
+        // ((wave 0 + wave 1) + wave 2) + wave 3, the last one straight to the block's partial rows
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            if (w == ww) {
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) {
+                    if (k0 + kk >= NB) continue;
+#pragma unroll
+                    for (int q = 0; q < NV / 4; ++q) {
+                        float4 a = make_float4(acc[kk][4 * q], acc[kk][4 * q + 1], acc[kk][4 * q + 2], acc[kk][4 * q + 3]);
+                        float4* r = reinterpret_cast<float4*>(red + kk * CH + 256 * q + 4 * lane);
+                        if (ww > 0) { const float4 o = *r; a.x = o.x + a.x; a.y = o.y + a.y; a.z = o.z + a.z; a.w = o.w + a.w; }
+                        if (ww < 3) *r = a;
+                        else *reinterpret_cast<float4*>(pblk + (size_t)(k0 + kk) * CH + 256 * q + 4 * lane) = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // lane 0's dots are the wave's per-pixel sums (wave_sum results are lane-uniform)
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) dot_l[w * 16 + k] = dots[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)
+        pblk[(size_t)NB * CH + threadIdx.x] = threadIdx.x < NB ? (dot_l[threadIdx.x] + dot_l[16 + threadIdx.x]) +
+                                                                  (dot_l[32 + threadIdx.x] + dot_l[48 + threadIdx.x]) : 0.f;
+}
+
+// dtext[k][c] from the blocks' partials: workgroup (x, k) sums columns 64 x .. 64 x + 63 of bin k and the bin's dot slot
+// over the blocks exactly as head_bias_finalize_kernel does (8 waves x 8 interleaved chains, combined in a fixed order),
+// then wave 0 applies exp(ls) and the F.normalize backward of text row k
+template <int CH>
+__global__ __launch_bounds__(512) void head_text_finalize_kernel(const float* __restrict__ part, int nblk, int NB,
+                                                                 const float* __restrict__ text, const float* logit_scale,
+                                                                 float* __restrict__ dtext)
+{
+    __shared__ float ws[8][64];
+    __shared__ float wd[8];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int k = blockIdx.y, c = blockIdx.x * 64 + lane;
+    const size_t stride = head_txt_stride(NB, CH);
+    const float* pc = part + (size_t)k * CH + c;
+    const float* pd = part + (size_t)NB * CH + k;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int b = w;
+    for (; b + 56 < nblk; b += 64) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s[j] += pc[(size_t)(b + 8 * j) * stride]; d[j] += pd[(size_t)(b + 8 * j) * stride]; }
+    }
+    for (int j = 0; b < nblk; b += 8, ++j) { s[j & 7] += pc[(size_t)b * stride]; d[j & 7] += pd[(size_t)b * stride]; }
+    ws[w][lane] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+    if (lane == 0) wd[w] = ((d[0] + d[1]) + (d[2] + d[3])) + ((d[4] + d[5]) + (d[6] + d[7]));
+    __syncthreads();
+    if (w == 0) {
+        float t = 0.f, dot = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { t += ws[j][lane]; dot += wd[j]; }
+        const float* tk = text + (size_t)k * CH;
+        float ss = 0.f;                                       // ||t_k||^2 in load_text's order
+#pragma unroll
+        for (int q = 0; q < CH / 256; ++q) {
+            const float4 x = *reinterpret_cast<const float4*>(tk + 256 * q + 4 * lane);
+            ss += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
+        }
+        const float nrm = sqrtf(wave_sum(ss));
+        const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+        const float dtn = expf(*logit_scale) * t;
+        dtext[(size_t)k * CH + c] = (nrm > 1e-12f ? dtn - (tk[c] * inv) * dot : dtn) * inv;
+    }
+}
+
 template <class T>
 __global__ void cast_kernel(const float* in, T* out, size_t n4)
 {
@@ -776,6 +955,46 @@ int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const 
         return head_bwd_t<1024>(dtype_z, dtype_dz, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dZ, dbias, dscale, P, HW,
                                 NB, ws, wsb, st);
     return EBC_E_UNSUPPORTED;
+}
+
+size_t head_bwd_text_ws_bytes(int P, int NB, int embed)
+{
+    if (P <= 0 || NB <= 0 || embed <= 0) return 0;
+    return (size_t)((P + HEAD_TXT_PPB - 1) / HEAD_TXT_PPB) * head_txt_stride(NB, embed) * sizeof(float);
+}
+
+template <int CH>
+static int head_bwd_text_t(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                           const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW,
+                           int NB, void* ws, hipStream_t st)
+{
+    constexpr int KB = head_txt_kb<CH>(), PPW = HEAD_TXT_PPB / 4;
+    const int nblk = (P + HEAD_TXT_PPB - 1) / HEAD_TXT_PPB;
+    float* part = reinterpret_cast<float*>(ws);
+    const size_t lds = ((size_t)NB * CH + KB * CH + 4 * PPW * 16 + 4 * PPW + 64) * 4;
+    constexpr int LDS_MAX = (16 * CH + KB * CH + 4 * PPW * 16 + 4 * PPW + 64) * 4;    // 69 KiB / 101 KiB
+    const ProbeScope probe(EBC_PROBE_HEAD_BWD_TEXT, 0, 0, 0, 0, P, NB, CH, st);
+    EBC_DTYPE_SWITCH(dtype_z,
+        if (!ensure_lds<head_text_bwd_kernel<T, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH;
+        hipLaunchKernelGGL((head_text_bwd_kernel<T, CH>), dim3(nblk), dim3(256), lds, st, (const T*)Z, text, logit_scale,
+                           anchors, dlogits, dexp, gscale, part, P, HW, NB));
+    EBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(head_text_finalize_kernel<CH>, dim3(CH / 64, NB), dim3(512), 0, st, part, nblk, NB, text, logit_scale,
+                       dtext);
+    EBC_CHECK_LAUNCH();
+    return EBC_OK;
+}
+
+int head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                  const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                  int embed, void* ws, size_t wsb, hipStream_t st)
+{
+    if (NB <= 0 || NB > 16 || (embed != 512 && embed != 1024)) return EBC_E_UNSUPPORTED;
+    if (dtype_z != EBC_F32 && dtype_z != EBC_F16 && dtype_z != EBC_BF16) return EBC_E_ARG;
+    if (!ws || wsb < head_bwd_text_ws_bytes(P, NB, embed)) return EBC_E_ARG;
+    if (embed == 512)
+        return head_bwd_text_t<512>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
+    return head_bwd_text_t<1024>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
 }
 
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st)

@@ -45,7 +45,8 @@ class EbcProbeRecord(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("kind", "epi", "bm", "bn", "mode", "m", "n", "k")] + [("ms", ctypes.c_float)]
 
 
-PROBE_KINDS = {1: "gemm", 2: "dace_loss", 3: "attn_fwd", 4: "attn_bwd_dq", 5: "attn_bwd_dkv", 6: "ln_fwd", 7: "ln_bwd"}
+PROBE_KINDS = {1: "gemm", 2: "dace_loss", 3: "attn_fwd", 4: "attn_bwd_dq", 5: "attn_bwd_dkv", 6: "ln_fwd", 7: "ln_bwd",
+               8: "head_bwd_text"}
 
 
 class EbcAugConst(ctypes.Structure):
@@ -91,6 +92,8 @@ SIGNATURES = {
     "ebc_head_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ebc_head_bwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "ebc_head_bwd_workspace_bytes": (_Z, [_I, _I]),
+    "ebc_head_bwd_text": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "ebc_head_bwd_text_workspace_bytes": (_Z, [_I, _I, _I]),
     "ebc_cast_f32": (_I, [_I, _P, _P, _Z, _P]),
     "ebc_im2col": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "ebc_tile_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

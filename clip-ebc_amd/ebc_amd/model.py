@@ -269,6 +269,7 @@ class _HeadFn(torch.autograd.Function):
             B, Hh, Ww, C = y.shape
         else:
             B, C, Hh, Ww = y.shape
+        text = text.detach().float().contiguous()                  # a buffer (frozen) or the text tower's output
         P, HW, NB = B * Hh * Ww, Hh * Ww, text.shape[0]
         dt = _lib.dtype_code(cdtype)
         if nhwc and y.dtype == cdtype and y.is_contiguous():
@@ -325,7 +326,14 @@ class _HeadFn(torch.autograd.Function):
                               P, C, E, st), "ebc_gemm(projection dX)")
         dW = _wgrad_rows(L, dZ, Y, cdtype, dev, st).reshape(wshape)
         dy = dY.view(B, Hh, Ww, C) if nhwc else dY.view(B, Hh, Ww, C).permute(0, 3, 1, 2).to(ydt)
-        return dy, dW, dbias, dscale.reshape(()), None, None, None, None
+        dtext = None
+        if ctx.needs_input_grad[4]:                                # a trainable text tower (model.py:201-208)
+            dtext = torch.empty(NB, E, device=dev, dtype=torch.float32)
+            wt = _dec_workspace(dev, L.ebc_head_bwd_text_workspace_bytes(P, NB, E), slot=3)
+            _lib.check(L.ebc_head_bwd_text(_lib.EBC_F32, _lib.ptr(Z), _lib.ptr(text), _lib.ptr(ls), _lib.ptr(anchors),
+                                           _lib.ptr(dl), _lib.ptr(de), None, _lib.ptr(dtext), P, HW, NB, E,
+                                           _lib.ptr(wt), wt.numel(), st), "ebc_head_bwd_text")
+        return dy, dW, dbias, dscale.reshape(()), dtext, None, None, None
 
 
 # ----------------------------------------------------------------------------- decoder
@@ -497,8 +505,12 @@ class CLIP_EBC(nn.Module):
         self.prompt_type = prompt_type
         self.text_encoder = CLIPTextEncoder(embed, 77, 49408, 512, 8, text_layers)
         self.freeze_text_encoder = freeze_text_encoder
-        for p in self.text_encoder.parameters():
-            p.requires_grad = False
+        if not freeze_text_encoder and text_features is not None:
+            raise ValueError("text_features= fixes the text features; with freeze_text_encoder=False they are computed "
+                             "by the trainable text encoder in every forward (models/clip/model.py:201)")
+        if freeze_text_encoder:                                    # models/clip/model.py:100-103
+            for p in self.text_encoder.parameters():
+                p.requires_grad = False
         self.bins = bins
         self.anchor_points = torch.tensor(anchor_points, dtype=torch.float32, requires_grad=False).view(1, -1, 1, 1)
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07), requires_grad=True)
@@ -530,9 +542,30 @@ class CLIP_EBC(nn.Module):
         if getattr(self, "_given_text", None) is not None:
             tf = torch.as_tensor(self._given_text, dtype=torch.float32)
         else:
-            tf = self.text_encoder(prompt_tokens(self.text_prompts).to(self.text_encoder.positional_embedding.device)).float()
+            with torch.no_grad():
+                tf = self.text_encoder(self._prompt_ids(self.text_encoder.positional_embedding.device)).float()
         with torch.no_grad():
             self.text_features.copy_(tf.to(self.text_features.device))
+
+    def _prompt_ids(self, device: torch.device) -> Tensor:
+        """The bin prompts' token ids on `device` (tokenised once; not a buffer, so the state-dict keys stay)."""
+        ids = getattr(self, "_prompt_ids_cache", None)
+        if ids is None or ids.device != device:
+            ids = prompt_tokens(self.text_prompts).to(device)
+            self._prompt_ids_cache = ids
+        return ids
+
+    def _text_operand(self) -> Tensor:
+        """The head's text features.  Frozen (default): the buffer computed once.  freeze_text_encoder=False
+        (models/clip/model.py:201): text_encoder(text_prompts) of THIS forward, under the caller's autocast, in train
+        and eval mode alike; _HeadFn returns its gradient (ebc_head_bwd_text) and autograd carries it into the text
+        tower.  The buffer keeps the detached value."""
+        if self.freeze_text_encoder:
+            return self.text_features
+        tf = self.text_encoder(self._prompt_ids(self.text_encoder.positional_embedding.device)).float()
+        with torch.no_grad():
+            self.text_features.copy_(tf)
+        return tf
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         res = super().load_state_dict(state_dict, strict=strict, assign=assign)
@@ -589,12 +622,13 @@ class CLIP_EBC(nn.Module):
         feat = feat.float().contiguous()                                     # NHWC rows, f32
         up = self.encoder_reduction // self.reduction
         blk = self.image_decoder[0]
+        text = self._text_operand()
         with torch.autocast("cuda", enabled=False):
             y = resnet._BottleneckFn.apply(feat, blk.conv1.weight, blk.conv2.weight, blk.conv3.weight, blk.bn1.weight,
                                     blk.bn1.bias, blk.bn2.weight, blk.bn2.bias, blk.bn3.weight, blk.bn3.bias, blk, up,
                                     cdt, self.training)
             logits, exp = _HeadFn.apply(y, self.projection.weight, self.projection.bias, self.logit_scale,
-                                        self.text_features, self._anchors, cdt, True)
+                                        text, self._anchors, cdt, True)
         return (logits, exp) if self.training else exp
 
     def forward(self, x: Tensor) -> Union[Tensor, Tuple[Tensor, Tensor]]:
@@ -607,11 +641,12 @@ class CLIP_EBC(nn.Module):
         feat = self._forward_vpt_nhwc(x)
         up = self.encoder_reduction // self.reduction                      # model.py:195-196 (B/16: x2, B/32: x4 at 8)
         blk = self.image_decoder[0]
+        text = self._text_operand()
         with torch.autocast("cuda", enabled=False):
             y = _DecoderFn.apply(feat, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight,
                                  blk.bn2.weight, blk.bn2.bias, blk, up, cdt, self.training)
             logits, exp = _HeadFn.apply(y, self.projection.weight, self.projection.bias, self.logit_scale,
-                                        self.text_features, self._anchors, cdt, True)
+                                        text, self._anchors, cdt, True)
         return (logits, exp) if self.training else exp
 
 

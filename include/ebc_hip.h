@@ -255,6 +255,21 @@ int ebc_head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, co
                  const float* anchors, const float* dlogits, const float* dexp, const float* gscale, void* dZ,
                  float* dbias, float* dscale, int P, int HW, int NB, int embed, void* workspace, size_t workspace_bytes,
                  ebc_stream_t stream);
+/* The head's gradient with respect to the text features, for a trainable text tower (freeze_text_encoder=False,
+ * models/clip/model.py:201-208: text_encoder(text_prompts) runs in every forward and its output is normalised inside the
+ * head, so the loss reaches every text parameter through it).  Same operands as ebc_head_bwd; writes
+ *   dtext [NB, embed] f32 = d (logits, exp) / d text, the RAW rows (the F.normalize backward of each row is applied:
+ *   dt_k = (g_k - tn_k <tn_k, g_k>) / max(||t_k||, 1e-12), g_k = exp(logit_scale) sum_p dl[p,k] zn_p; g_k / 1e-12 for a
+ *   row whose norm is at or below the clamp).
+ * Deterministic: per-workgroup partial sums in `workspace` (ebc_head_bwd_text_workspace_bytes(P, NB, embed) bytes, plain
+ * stores), then a fixed-order sum; no float atomics.  A launch of its own: ebc_head_bwd and its outputs do not change.
+ * EBC_E_ARG, before any device work: NULL Z / text / logit_scale / anchors / dlogits / dexp / dtext, P <= 0, HW <= 0,
+ * P % HW != 0, a dtype_z that is none of the three, a workspace that is NULL or too small.  EBC_E_UNSUPPORTED, before any
+ * device work: NB outside 1..16, embed other than 512 / 1024 (the workspace size of such a call is 0). */
+size_t ebc_head_bwd_text_workspace_bytes(int P, int NB, int embed);
+int ebc_head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                      const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                      int embed, void* workspace, size_t workspace_bytes, ebc_stream_t stream);
 int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream);
 /* Patch rows of the patch-embedding GEMM (conv1 as im2col-GEMM, image_encoder.py:141): x [B,3,H,W] f32 ->
  * out [B*(H/patch)*(W/patch), 3*patch*patch] of dtype, column k = c*patch*patch + kh*patch + kw (conv1.weight's
@@ -485,7 +500,7 @@ int ebc_set_weight_touch(int mode);
  *   launch (returns the number recorded; records beyond `capacity` are dropped).
  * ebc_marker(id, stream): launches the named empty kernel `ebc_marker_kernel` (profile window edges). */
 enum { EBC_PROBE_GEMM = 1, EBC_PROBE_DACE = 2, EBC_PROBE_ATTN_FWD = 3, EBC_PROBE_ATTN_BWD_DQ = 4,
-       EBC_PROBE_ATTN_BWD_DKV = 5, EBC_PROBE_LN_FWD = 6, EBC_PROBE_LN_BWD = 7 };
+       EBC_PROBE_ATTN_BWD_DKV = 5, EBC_PROBE_LN_FWD = 6, EBC_PROBE_LN_BWD = 7, EBC_PROBE_HEAD_BWD_TEXT = 8 };
 typedef struct {
     int kind;                 /* EBC_PROBE_* */
     int epi, bm, bn, mode;    /* GEMM: epilogue, tile, MODE (0 plain, 1 implicit 3x3 conv, 2 conv weight gradient) */

@@ -1,10 +1,16 @@
 """Train-step throughput of a CLIP ViT backbone on one MI355X, for backbones bench.py does not time (clip_vit_b_32):
 
     python tools/bench_vit_step.py [--model clip_vit_b_32] [--crops 16] [--steps 60] [--warmup 15] [--dtype fp16]
+                                   [--train-text]
 
 The step is bench.py's (model forward under autocast, DACE/DMCount loss, backward, the HIP Adam + GradScaler step) on
 bench.py's synthetic crops; each timed step sits between two device events and the median over the timed steps is
-reported (crops/s = crops / median), with the spread, as one JSON line.  No GPU: an error, not a CPU time."""
+reported (crops/s = crops / median), with the spread, as one JSON line.  No GPU: an error, not a CPU time.
+
+--train-text builds the model with freeze_text_encoder=False (the text tower runs in every forward and takes gradients
+through ebc_head_bwd_text) and adds to the line: the launch's in-step time from one probed step (ebc_probe_begin / _end),
+its isolated time at the step's shape, its partial-buffer bytes, and the text tower's own forward + backward under the
+same autocast (PyTorch-ROCm; events around it, median)."""
 from __future__ import annotations
 
 import argparse
@@ -24,6 +30,57 @@ BINS = [(0.0, 0.0), (1.0, 1.0), (2.0, 2.0), (3.0, 3.0), (4.0, float("inf"))]
 ANCHORS_NWPU = [0.0, 1.0, 2.0, 3.0, 4.21931]
 
 
+def _median_ms(fn, n=30, warm=5):
+    for _ in range(warm):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return float(np.median([a.elapsed_time(b) for a, b in ev]))
+
+
+def _text_cost(model, step, args, amp, dev):
+    """What --train-text adds to a step, split into the new launch and the PyTorch text tower."""
+    import ctypes
+    from ebc_amd import _lib
+    L = _lib.lib()
+    cap = 4096
+    _lib.check(L.ebc_probe_begin(cap), "ebc_probe_begin")
+    step(0)
+    recs = (_lib.EbcProbeRecord * cap)()
+    n = L.ebc_probe_end(ctypes.cast(recs, ctypes.c_void_p), cap)
+    in_step = [r.ms for r in recs[:min(n, cap)] if _lib.PROBE_KINDS.get(r.kind) == "head_bwd_text"]
+    g = (224 // args.reduction) ** 2
+    P, NB, E = args.crops * g, len(BINS), model.clip_embed_dim
+    gen = torch.Generator(device=dev).manual_seed(1)
+    Z = torch.randn(P, E, device=dev, generator=gen)
+    text = torch.randn(NB, E, device=dev, generator=gen)
+    dl = torch.randn(args.crops, NB, g, device=dev, generator=gen)
+    de = torch.randn(args.crops, g, device=dev, generator=gen)
+    ls, anchors = torch.full((1,), 2.659, device=dev), torch.tensor(ANCHORS_NWPU, device=dev)
+    need = L.ebc_head_bwd_text_workspace_bytes(P, NB, E)
+    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    dtext = torch.empty(NB, E, device=dev)
+    p, st = _lib.ptr, _lib.stream(dev)
+    iso = _median_ms(lambda: _lib.check(L.ebc_head_bwd_text(_lib.EBC_F32, p(Z), p(text), p(ls), p(anchors), p(dl), p(de),
+                                                            None, p(dtext), P, g, NB, E, p(ws), need, st), "head_bwd_text"))
+    ids = model._prompt_ids(dev)
+    gt = torch.randn(NB, E, device=dev, generator=gen)
+
+    def tower():
+        with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
+            tf = model.text_encoder(ids).float()
+        tf.backward(gt)
+    tower_ms = _median_ms(tower)
+    model.zero_grad(set_to_none=True)
+    return {"head_bwd_text_ms_in_step": [round(v, 4) for v in in_step], "head_bwd_text_ms_isolated": round(iso, 4),
+            "head_bwd_text_partial_bytes": int(need), "text_tower_fwd_bwd_ms": round(tower_ms, 3),
+            "trainable_params": int(sum(q.numel() for q in model.parameters() if q.requires_grad))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="clip_vit_b_32", choices=["clip_vit_b_32", "clip_vit_b_16"])
@@ -32,6 +89,7 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "fp32"])
+    ap.add_argument("--train-text", action="store_true", help="freeze_text_encoder=False")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_vit_step.py needs a HIP device")
@@ -42,7 +100,8 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(42)
     model = get_model(args.model, 224, args.reduction, BINS, ANCHORS_NWPU, prompt_type="word", num_vpt=32,
-                      vpt_drop=0.0, deep_vpt=True, weights_seed=0).to(dev).train()
+                      vpt_drop=0.0, deep_vpt=True, weights_seed=0,
+                      freeze_text_encoder=not args.train_text).to(dev).train()
     loss_fn = DACELoss(BINS, args.reduction, weight_count_loss=1.0, count_loss="dmcount", input_size=224).to(dev)
     params = [p for p in model.parameters() if p.requires_grad]
     amp = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": None}[args.dtype]
@@ -78,13 +137,15 @@ def main():
     assert bool(torch.isfinite(loss)), "the last step's loss is not finite"
     med = float(np.median(ms))
     wall = ev[0][0].elapsed_time(ev[-1][1]) / args.steps          # first start to last end: includes the gaps between steps
+    extra = _text_cost(model, step, args, amp, dev) if args.train_text else {}
     print(json.dumps({"metric": f"train crops/s {args.model} 224px reduction {args.reduction}, {args.crops} crops, "
-                                f"{args.dtype} autocast, full step (fwd + DACE/DMCount + bwd + Adam)",
+                                f"{args.dtype} autocast, full step (fwd + DACE/DMCount + bwd + Adam)"
+                                + (", trainable text tower" if args.train_text else ""),
                       "value": round(args.crops / med * 1e3, 1), "unit": "crops/s", "step_ms_median": round(med, 3),
                       "step_ms_window_mean": round(wall, 3),
                       "step_ms_p10": round(float(np.percentile(ms, 10)), 3),
                       "step_ms_p90": round(float(np.percentile(ms, 90)), 3), "steps": args.steps,
-                      "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}))
+                      "warmup": args.warmup, "device": torch.cuda.get_device_name(0), **extra}))
 
 
 if __name__ == "__main__":
