@@ -743,13 +743,19 @@ inline int grid_for(size_t n, int block = 256) {
 // ------------------------------------------------------------------------------- launchers
 namespace ebc {
 
+// D = 768 (the ViT) or 512 (the text tower): NV = D / 256 float4 a lane
 static int ln_fwd_launch(int dtype, const float* x, RowMap map, const float* gamma, const float* beta, void* out,
-                         float* outf, float* mean, float* rstd, int M, VptIns vi, hipStream_t st)
+                         float* outf, float* mean, float* rstd, int M, VptIns vi, hipStream_t st, int D = 768)
 {
     const dim3 grid((M + 3) / 4);
-    const ProbeScope probe(EBC_PROBE_LN_FWD, 0, 0, 0, 0, M, 768, 0, st);
-    EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_fwd_kernel<T, 3>), grid, dim3(256), 0, st, x, map, gamma, beta, (T*)out,
-                                               outf, mean, rstd, M, vi));
+    const ProbeScope probe(EBC_PROBE_LN_FWD, 0, 0, 0, 0, M, D, 0, st);
+    if (D == 512) {
+        EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_fwd_kernel<T, 2>), grid, dim3(256), 0, st, x, map, gamma, beta,
+                                                   (T*)out, outf, mean, rstd, M, vi));
+    } else {
+        EBC_DTYPE_SWITCH(dtype, hipLaunchKernelGGL((ln_fwd_kernel<T, 3>), grid, dim3(256), 0, st, x, map, gamma, beta,
+                                                   (T*)out, outf, mean, rstd, M, vi));
+    }
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -757,9 +763,9 @@ static int ln_fwd_launch(int dtype, const float* x, RowMap map, const float* gam
 int layernorm_fwd(int dtype, const float* x, int rpg, int gstride, int goff, const float* gamma, const float* beta,
                   void* out, float* outf, float* mean, float* rstd, int M, int D, hipStream_t st)
 {
-    if (D != 768 || M <= 0) return EBC_E_UNSUPPORTED;
+    if ((D != 768 && D != 512) || M <= 0) return EBC_E_UNSUPPORTED;
     const RowMap map{rpg > 0 ? rpg : M, gstride, goff};
-    return ln_fwd_launch(dtype, x, map, gamma, beta, out, outf, mean, rstd, M, VptIns{nullptr, 0, 1, 0, nullptr}, st);
+    return ln_fwd_launch(dtype, x, map, gamma, beta, out, outf, mean, rstd, M, VptIns{nullptr, 0, 1, 0, nullptr}, st, D);
 }
 
 int layernorm_fwd_vpt(int dtype, float* X, const float* vpt, long vpt_bstride, int L, int NVPT, const float* gamma,
@@ -771,16 +777,16 @@ int layernorm_fwd_vpt(int dtype, float* X, const float* vpt, long vpt_bstride, i
                          VptIns{vpt, vpt_bstride, L, NVPT, X}, st);
 }
 
-template <class T>
+template <class T, int NV = 3>
 static int ln_bwd_t(int dy_f32, const void* dy, const float* x, RowMap map, const float* mean, const float* rstd,
                     const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, VptOut vo, hipStream_t st)
 {
     const dim3 grid((M + 3) / 4);
-    const ProbeScope probe(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 768, 0, st);
+    const ProbeScope probe(EBC_PROBE_LN_BWD, 0, 0, 0, 0, M, 256 * NV, 0, st);
     if (dy_f32)
-        hipLaunchKernelGGL((ln_bwd_kernel<T, float, 3>), grid, dim3(256), 0, st, (const float*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (T*)dx_out_t, M, vo, TouchList{});
+        hipLaunchKernelGGL((ln_bwd_kernel<T, float, NV>), grid, dim3(256), 0, st, (const float*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (T*)dx_out_t, M, vo, TouchList{});
     else
-        hipLaunchKernelGGL((ln_bwd_kernel<T, T, 3>), grid, dim3(256), 0, st, (const T*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (T*)dx_out_t, M, vo, TouchList{});
+        hipLaunchKernelGGL((ln_bwd_kernel<T, T, NV>), grid, dim3(256), 0, st, (const T*)dy, x, map, mean, rstd, gamma, dx_in, dx_out, (T*)dx_out_t, M, vo, TouchList{});
     EBC_CHECK_LAUNCH();
     return EBC_OK;
 }
@@ -813,10 +819,13 @@ int layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int rpg
                   const float* mean, const float* rstd, const float* gamma, const float* dx_in, float* dx_out,
                   void* dx_out_t, int M, int D, hipStream_t st)
 {
-    if (D != 768 || M <= 0) return EBC_E_UNSUPPORTED;
+    if ((D != 768 && D != 512) || M <= 0) return EBC_E_UNSUPPORTED;
     const RowMap map{rpg > 0 ? rpg : M, gstride, goff};
     const VptOut vo{nullptr, 1, 0};
     // f32: dy is always f32
+    if (D == 512)
+        EBC_DTYPE_SWITCH(dtype, return (ln_bwd_t<T, 2>(E::BYTES == 4 ? 1 : dy_f32, dy, x, map, mean, rstd, gamma, dx_in,
+                                                       dx_out, dx_out_t, M, vo, st)));
     EBC_DTYPE_SWITCH(dtype, return ln_bwd_t<T>(E::BYTES == 4 ? 1 : dy_f32, dy, x, map, mean, rstd, gamma, dx_in, dx_out,
                                                dx_out_t, M, vo, st));
 }

@@ -61,6 +61,28 @@ class EbcAdamTensor(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_long)]
 
 
+_TEXT_LAYER_FIELDS = ("w_qkv", "b_qkv", "w_out", "b_out", "w_fc", "b_fc", "w_proj", "b_proj", "ln1_g", "ln1_b", "ln2_g",
+                      "ln2_b")
+
+
+class EbcTextLayer(ctypes.Structure):
+    """include/ebc_hip.h EbcTextLayer / EbcTextLayerGrads (one block's f32 parameters, or their gradients)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in _TEXT_LAYER_FIELDS]
+
+
+class EbcTextWeights(ctypes.Structure):
+    """include/ebc_hip.h EbcTextWeights."""
+    _fields_ = [(n, ctypes.c_int) for n in ("layers", "width", "heads", "embed", "vocab", "context")] + \
+               [(n, ctypes.c_void_p) for n in ("token_embedding", "positional_embedding", "ln_final_g", "ln_final_b",
+                                               "text_projection")] + [("layer", ctypes.POINTER(EbcTextLayer))]
+
+
+class EbcTextGrads(ctypes.Structure):
+    """include/ebc_hip.h EbcTextGrads."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("token_embedding", "positional_embedding", "ln_final_g", "ln_final_b",
+                                               "text_projection")] + [("layer", ctypes.POINTER(EbcTextLayer))]
+
+
 # name -> (restype, argtypes); must mirror include/ebc_hip.h
 SIGNATURES = {
     "ebc_version": (_I, []),
@@ -95,6 +117,15 @@ SIGNATURES = {
     "ebc_head_bwd_text": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "ebc_head_bwd_text_workspace_bytes": (_Z, [_I, _I, _I]),
     "ebc_cast_f32": (_I, [_I, _P, _P, _Z, _P]),
+    "ebc_attention_causal_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _P]),
+    "ebc_attention_causal_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ebc_layernorm_param_grad": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "ebc_colsum": (_I, [_I, _I, _P, _P, _I, _I, _P]),
+    "ebc_text_embed_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ebc_text_embed_bwd": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ebc_text_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "ebc_text_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
+    "ebc_text_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
     "ebc_im2col": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "ebc_tile_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ebc_tile_assemble": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -451,8 +451,10 @@ class CLIP_EBC(nn.Module):
                  input_size: Optional[int] = None, num_vpt: Optional[int] = None, deep_vpt: Optional[bool] = None,
                  vpt_drop: Optional[float] = None, decoder_cfg: Optional[List[int]] = None, vit_layers: int = 12,
                  text_layers: int = 12, text_features: Optional[Tensor] = None, weights_seed: Optional[int] = None,
-                 **kwargs: Any) -> None:
+                 text_tower: str = "torch", **kwargs: Any) -> None:
         super().__init__()
+        if text_tower not in ("torch", "hip"):
+            raise ValueError(f"text_tower must be 'torch' or 'hip', got {text_tower!r}")
         if backbone in ("vit_l_14", "vit_l_14_336px"):
             raise NotImplementedError(f"backbone {backbone!r}: the HIP encoder is built for width 768 / 12 heads and patch "
                                       "16 or 32; ViT-L/14 needs width 1024 (16 heads, MLP 4096) in the LayerNorm and "
@@ -503,7 +505,11 @@ class CLIP_EBC(nn.Module):
         self.channels, self.clip_embed_dim = decoder_cfg[-1], embed
         self.projection = nn.Conv2d(self.channels, embed, kernel_size=1)
         self.prompt_type = prompt_type
-        self.text_encoder = CLIPTextEncoder(embed, 77, 49408, 512, 8, text_layers)
+        # text_tower="hip": the trainable tower runs in the library (ebc_text_forward / ebc_text_backward); frozen, the
+        # features are computed once at construction and the choice has no effect
+        self.text_tower = text_tower
+        self.text_encoder = CLIPTextEncoder(embed, 77, 49408, 512, 8, text_layers,
+                                            impl="torch" if freeze_text_encoder else text_tower)
         self.freeze_text_encoder = freeze_text_encoder
         if not freeze_text_encoder and text_features is not None:
             raise ValueError("text_features= fixes the text features; with freeze_text_encoder=False they are computed "

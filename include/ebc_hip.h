@@ -208,7 +208,8 @@ int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int dtype, voi
                      size_t workspace_bytes, const float* dfeat, float* const* dvpt, long vpt_bstride, int flags,
                      ebc_stream_t stream);
 
-/* LayerNorm over 768 channels (models/clip/_clip/blocks.py:8-14, fp32 math, eps 1e-5).
+/* LayerNorm over D = 768 (the ViT) or 512 (the text tower) channels (models/clip/_clip/blocks.py:8-14, fp32 math, eps
+ * 1e-5); any other D: EBC_E_UNSUPPORTED.
  * Row r of the output reads input row (r / rows_per_group) * group_stride + group_offset +
  * r % rows_per_group (rows_per_group = 0: identity), e.g. ln_post on the patch rows only.
  * The map is one-sided: the forward reads x at the mapped row and writes out / out_f32 / mean / rstd dense (row r);
@@ -271,6 +272,91 @@ int ebc_head_bwd_text(int dtype_z, const void* Z, const float* text, const float
                       const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
                       int embed, void* workspace, size_t workspace_bytes, ebc_stream_t stream);
 int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CLIP text tower, trained (freeze_text_encoder=False, models/clip/model.py:100-115,201): CLIPTextEncoder
+ * (models/clip/_clip/text_encoder.py:7-53) over ResidualAttentionBlock (blocks.py:22-42) with the causal mask
+ * (text_encoder.py:33-39), forward and the backward of every parameter.  Width 512, 8 heads of 64, context <= 77.
+ *
+ * The text feature of prompt k is row eot_k of its tokens and the mask is causal, so rows past a prompt's EOT never reach
+ * the output and take exactly zero gradient: the tower runs Lt = max_k eot_k + 1 tokens a prompt (ids [NB][Lt], the
+ * first Lt of each prompt's context tokens).  This is exact.
+ *
+ * Kernels (text.hip).  No float atomics: every sum runs in a fixed order and two launches agree bit for bit.
+ *   ebc_attention_causal_fwd / _bwd: ebc_attention_fwd / _bwd with keys j <= i only, L <= 77 (EBC_E_UNSUPPORTED above),
+ *     one workgroup per (prompt, head); delta_ws is never touched (NULL is fine), lse may be NULL in the forward.
+ *     EBC_E_ARG: NULL qkv / out (forward) or qkv / dout / out / lse / dqkv (backward), B, L or H <= 0, a bad dtype.
+ *   ebc_layernorm_param_grad: dgamma[c] = sum_r dy[r][c] xhat[r][c], dbeta[c] = sum_r dy[r][c] over M dense rows, xhat =
+ *     (x - mean[r]) rstd[r]; dy of dtype, or f32 when dy_f32.  D 512 or 768 (EBC_E_UNSUPPORTED otherwise); EBC_E_ARG: a
+ *     NULL pointer, M <= 0, a bad dtype.
+ *   ebc_colsum: out[c] = sum_r a[r][c] for a [M][N] of dtype (f32 when in_f32): the bias gradients.  EBC_E_ARG: NULL a /
+ *     out, M or N <= 0, a bad dtype.
+ *     Both sum rows r = g (mod 8) in ascending order for g = 0 .. 7, then the eight partial sums in that order.
+ *   ebc_text_embed_fwd: x[p][t] = token_embedding[ids[p][t]] + positional_embedding[t] (text_encoder.py:42-44), t < Lt.
+ *   ebc_text_embed_bwd: the dense gradients, every element written: dtoken [vocab][512], row v = the sum of the dx rows
+ *     rows[offs[u] .. offs[u + 1]) in list order where v = uniq[u], zero for a v not in uniq; dpos [context][512], row t =
+ *     sum_p dx[p][t] in prompt order, zero for t >= Lt.  uniq [nu] ascending, offs [nu + 1], rows [NB * Lt] (values p * Lt
+ *     + t) are device arrays the caller builds once from the ids (the inverted index of the embedding gather).
+ *     Both: EBC_E_ARG for a NULL pointer, vocab <= 0 (and context < Lt or > 77, nu outside 1 .. NB * Lt in the backward);
+ *     EBC_E_UNSUPPORTED for NB outside 1 .. 16, Lt outside 1 .. 77, width other than 512. */
+int ebc_attention_causal_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream);
+int ebc_attention_causal_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
+                             float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream);
+int ebc_layernorm_param_grad(int dtype, int dy_f32, const void* dy, const float* x, const float* mean, const float* rstd,
+                             float* dgamma, float* dbeta, int M, int D, ebc_stream_t stream);
+int ebc_colsum(int dtype, int in_f32, const void* a, float* out, int M, int N, ebc_stream_t stream);
+int ebc_text_embed_fwd(const float* token_embedding, const float* positional_embedding, const int* ids, float* x, int NB,
+                       int Lt, int width, int vocab, ebc_stream_t stream);
+int ebc_text_embed_bwd(const float* dx, const int* uniq, const int* offs, const int* rows, int nu, float* dtoken,
+                       float* dpos, int NB, int Lt, int context, int width, int vocab, ebc_stream_t stream);
+
+/* The whole tower, one call each way.  Every parameter is the f32 tensor being trained (device memory; the structs
+ * themselves live in HOST memory): the parameters change every step, so each forward makes its compute-dtype and
+ * transposed copies in the workspace.  The residual stream, its gradient and the LayerNorm statistics are f32, GEMM and
+ * attention operands are of `dtype`.
+ *   ids [NB][Lt] int32, eot [NB] int32 (the EOT position of each prompt, < Lt): device arrays.
+ *   features [NB][embed] f32 = ln_final(x)[k, eot_k] @ text_projection (text_encoder.py:50-52).
+ *   training 1 keeps every layer's activations in the workspace for ebc_text_backward, which must be given the same
+ *   workspace, untouched, and the same w, ids, eot, NB, Lt and dtype; 0 keeps nothing.
+ *   ebc_text_backward writes EVERY gradient in g (f32, the parameters' shapes; the embedding gradients dense, zero rows
+ *   included) from dfeatures [NB][embed] f32; uniq / offs / rows / nu as for ebc_text_embed_bwd.
+ * EBC_E_ARG, before any device work: a NULL pointer (structs, their fields, ids, eot, workspace, features / dfeatures, the
+ * index arrays), layers <= 0, heads != 8, vocab <= 0, context < Lt or > 77, nu outside 1 .. NB * Lt, a bad dtype, a
+ * workspace smaller than ebc_text_workspace_bytes.  EBC_E_UNSUPPORTED, before any device work: NB outside 1 .. 16, Lt
+ * outside 1 .. 77, width other than 512, embed other than 512 / 1024 (the workspace size of such a call is 0). */
+typedef struct {
+    const float* w_qkv;  const float* b_qkv;    /* attn.in_proj_weight [1536,512], in_proj_bias */
+    const float* w_out;  const float* b_out;    /* attn.out_proj [512,512] */
+    const float* w_fc;   const float* b_fc;     /* mlp.c_fc [2048,512] */
+    const float* w_proj; const float* b_proj;   /* mlp.c_proj [512,2048] */
+    const float* ln1_g; const float* ln1_b; const float* ln2_g; const float* ln2_b;
+} EbcTextLayer;
+typedef struct {
+    int layers, width, heads, embed, vocab, context;   /* width 512, heads 8, embed 512 | 1024, context <= 77 */
+    const float* token_embedding;                      /* [vocab, 512] */
+    const float* positional_embedding;                 /* [context, 512] */
+    const float* ln_final_g; const float* ln_final_b;
+    const float* text_projection;                      /* [512, embed] */
+    const EbcTextLayer* layer;                         /* host array [layers] */
+} EbcTextWeights;
+typedef struct {
+    float* w_qkv;  float* b_qkv;
+    float* w_out;  float* b_out;
+    float* w_fc;   float* b_fc;
+    float* w_proj; float* b_proj;
+    float* ln1_g; float* ln1_b; float* ln2_g; float* ln2_b;
+} EbcTextLayerGrads;
+typedef struct {
+    float* token_embedding; float* positional_embedding; float* ln_final_g; float* ln_final_b; float* text_projection;
+    const EbcTextLayerGrads* layer;                    /* host array [layers] */
+} EbcTextGrads;
+size_t ebc_text_workspace_bytes(int NB, int Lt, int layers, int embed, int dtype, int training);
+int ebc_text_forward(const EbcTextWeights* w, const int* ids, const int* eot, int NB, int Lt, int dtype, int training,
+                     void* workspace, size_t workspace_bytes, float* features, ebc_stream_t stream);
+int ebc_text_backward(const EbcTextWeights* w, const EbcTextGrads* g, const int* ids, const int* eot, const int* uniq,
+                      const int* offs, const int* rows, int nu, int NB, int Lt, int dtype, void* workspace,
+                      size_t workspace_bytes, const float* dfeatures, ebc_stream_t stream);
+
 /* Patch rows of the patch-embedding GEMM (conv1 as im2col-GEMM, image_encoder.py:141): x [B,3,H,W] f32 ->
  * out [B*(H/patch)*(W/patch), 3*patch*patch] of dtype, column k = c*patch*patch + kh*patch + kw (conv1.weight's
  * order); patch % 4 == 0 and 3*patch*patch <= 4096 (one float4 a lane, up to 1024 lanes a row). */

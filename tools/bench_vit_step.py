@@ -1,7 +1,7 @@
 """Train-step throughput of a CLIP ViT backbone on one MI355X, for backbones bench.py does not time (clip_vit_b_32):
 
     python tools/bench_vit_step.py [--model clip_vit_b_32] [--crops 16] [--steps 60] [--warmup 15] [--dtype fp16]
-                                   [--train-text]
+                                   [--train-text [--text-tower {torch,hip}]]
 
 The step is bench.py's (model forward under autocast, DACE/DMCount loss, backward, the HIP Adam + GradScaler step) on
 bench.py's synthetic crops; each timed step sits between two device events and the median over the timed steps is
@@ -10,7 +10,9 @@ reported (crops/s = crops / median), with the spread, as one JSON line.  No GPU:
 --train-text builds the model with freeze_text_encoder=False (the text tower runs in every forward and takes gradients
 through ebc_head_bwd_text) and adds to the line: the launch's in-step time from one probed step (ebc_probe_begin / _end),
 its isolated time at the step's shape, its partial-buffer bytes, and the text tower's own forward + backward under the
-same autocast (PyTorch-ROCm; events around it, median)."""
+same autocast (events around it, median).  --text-tower hip runs that tower in the library (text_tower="hip":
+ebc_text_forward / ebc_text_backward) instead of PyTorch-ROCm; the line then also carries the tower's host enqueue time
+(the same forward + backward timed on the host clock without a device wait, median) beside its device time."""
 from __future__ import annotations
 
 import argparse
@@ -75,8 +77,17 @@ def _text_cost(model, step, args, amp, dev):
             tf = model.text_encoder(ids).float()
         tf.backward(gt)
     tower_ms = _median_ms(tower)
+    import time
+    host = []
+    for _ in range(20):                      # enqueue cost alone: the device runs behind, the queue is drained between calls
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tower()
+        host.append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
     model.zero_grad(set_to_none=True)
-    return {"head_bwd_text_ms_in_step": [round(v, 4) for v in in_step], "head_bwd_text_ms_isolated": round(iso, 4),
+    return {"text_tower": args.text_tower, "text_tower_host_enqueue_ms": round(float(np.median(host)), 3),
+            "head_bwd_text_ms_in_step": [round(v, 4) for v in in_step], "head_bwd_text_ms_isolated": round(iso, 4),
             "head_bwd_text_partial_bytes": int(need), "text_tower_fwd_bwd_ms": round(tower_ms, 3),
             "trainable_params": int(sum(q.numel() for q in model.parameters() if q.requires_grad))}
 
@@ -90,6 +101,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=15)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "fp32"])
     ap.add_argument("--train-text", action="store_true", help="freeze_text_encoder=False")
+    ap.add_argument("--text-tower", default="torch", choices=["torch", "hip"],
+                    help="with --train-text: the text tower on PyTorch-ROCm or in the library (text_tower=)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_vit_step.py needs a HIP device")
@@ -101,7 +114,7 @@ def main():
     torch.manual_seed(42)
     model = get_model(args.model, 224, args.reduction, BINS, ANCHORS_NWPU, prompt_type="word", num_vpt=32,
                       vpt_drop=0.0, deep_vpt=True, weights_seed=0,
-                      freeze_text_encoder=not args.train_text).to(dev).train()
+                      freeze_text_encoder=not args.train_text, text_tower=args.text_tower).to(dev).train()
     loss_fn = DACELoss(BINS, args.reduction, weight_count_loss=1.0, count_loss="dmcount", input_size=224).to(dev)
     params = [p for p in model.parameters() if p.requires_grad]
     amp = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": None}[args.dtype]
@@ -140,7 +153,7 @@ def main():
     extra = _text_cost(model, step, args, amp, dev) if args.train_text else {}
     print(json.dumps({"metric": f"train crops/s {args.model} 224px reduction {args.reduction}, {args.crops} crops, "
                                 f"{args.dtype} autocast, full step (fwd + DACE/DMCount + bwd + Adam)"
-                                + (", trainable text tower" if args.train_text else ""),
+                                + (f", trainable text tower ({args.text_tower})" if args.train_text else ""),
                       "value": round(args.crops / med * 1e3, 1), "unit": "crops/s", "step_ms_median": round(med, 3),
                       "step_ms_window_mean": round(wall, 3),
                       "step_ms_p10": round(float(np.percentile(ms, 10)), 3),
