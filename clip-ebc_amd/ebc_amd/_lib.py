@@ -40,6 +40,17 @@ class EbcCropDesc(ctypes.Structure):
                 ("seed", ctypes.c_uint32), ("normalize", ctypes.c_int32), ("hue", ctypes.c_float)]
 
 
+EBC_EVAL_U8_HWC, EBC_EVAL_U8_CHW, EBC_EVAL_F32_CHW = 0, 1, 2
+
+
+class EbcEvalImage(ctypes.Structure):
+    """include/ebc_hip.h EbcEvalImage (one image of a raw evaluation batch)."""
+    _fields_ = [("src_off", ctypes.c_int64), ("map_off", ctypes.c_int64),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Hf", ctypes.c_int32), ("Wf", ctypes.c_int32),
+                ("tile0", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("layout", ctypes.c_int32)]
+
+
 class EbcProbeRecord(ctypes.Structure):
     """include/ebc_hip.h EbcProbeRecord (one instrumented launch)."""
     _fields_ = [(n, ctypes.c_int) for n in ("kind", "epi", "bm", "bn", "mode", "m", "n", "k")] + [("ms", ctypes.c_float)]
@@ -129,6 +140,9 @@ SIGNATURES = {
     "ebc_im2col": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
     "ebc_tile_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ebc_tile_assemble": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ebc_tiles_from_raw": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "ebc_u8_to_chw01": (_I, [_P, _I, _I, _I, _P, _P]),
+    "ebc_tiles_assemble_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ebc_dec_geometry": (_I, [_I, _I, _I, _I, _I, _P]),
     "ebc_dec_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "ebc_dec_upsample_pad": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -371,6 +371,45 @@ int ebc_tile_gather(const float* image, float* tiles, int C, int H, int W, int w
 int ebc_tile_assemble(const float* preds, float* out, int Cp, int H, int W, int wh, int ww, int sh, int sw,
                       int reduction, ebc_stream_t stream);
 
+/* Evaluation of a split from raw images (datasets/crowd.py:141-162, datasets/transforms.py:69-134,
+ * utils/eval_utils.py:26-96, eval.py:27).  One descriptor per image; the tile list is global and runs across the
+ * images in order (image i owns tiles tile0 .. tile0 + rows*cols, tile0 = the tiles before it), so a model batch
+ * may span images.  The tiling is ebc_tile_gather's, on the fitted size Hf x Wf (rows/cols = ceil((Hf-wh)/sh)+1).
+ *   layout U8_HWC   [H][W][3] bytes (a decoded JPEG);  U8_CHW  [3][H][W] bytes (the reference's .npy images)
+ *          F32_CHW  [3][H][W] f32 already normalised (a resized image: ebc_u8_to_chw01, then one ebc_augment_crops
+ *                   descriptor whose crop is the whole image, out_h x out_w the fitted size, normalize = 1)
+ * Both batch entry points take the descriptor array twice, on the device (what the kernels read) and on the host
+ * (what the checks and the grid sizes read; only read during the call).
+ * EBC_E_ARG, before any device work: a NULL pointer, Hf < wh or Wf < ww, Hf < H or Wf < W, a layout that is none of
+ * the three, rows / cols / tile0 that are not the tiling's, a tile range outside the list, ww % 4, a src that is not
+ * 4-byte or tiles that are not 16-byte aligned, an F32_CHW src_off % 4, and any size past int32 (3 Hf Wf of an
+ * image, the tile count, 3 wh ww tile_count, the elements of preds or of the maps). */
+enum { EBC_EVAL_U8_HWC = 0, EBC_EVAL_U8_CHW = 1, EBC_EVAL_F32_CHW = 2 };
+typedef struct {
+    int64_t src_off;                     /* byte offset of the image in src */
+    int64_t map_off;                     /* element offset of its assembled map [Cp][Hf/r][Wf/r] in maps */
+    int32_t H, W;                        /* stored size */
+    int32_t Hf, Wf;                      /* fitted size (>= stored: the rest is ZeroPad2Multiple's right/bottom zeros) */
+    int32_t tile0, rows, cols;
+    int32_t layout;
+} EbcEvalImage;
+/* tiles [tile_count][3][wh][ww] f32 <- tiles tile_begin .. + tile_count of the global list.  u8 sources:
+ * ((float)u / 255 - mean[c]) / std[c], three f32 operations, bit-equal to the reference's CPU tensors; pixels with
+ * y >= H or x >= W are (0 - mean[c]) / std[c] (fill = 0 before Normalize).  mean / std: 3 host floats each.  src is
+ * read in aligned dwords, so its allocation ends on a multiple of 4 bytes. */
+int ebc_tiles_from_raw(const void* src, const EbcEvalImage* desc, const EbcEvalImage* desc_host, int n_images, int wh,
+                       int ww, int sh, int sw, int tile_begin, int tile_count, const float* mean, const float* std,
+                       float* tiles, ebc_stream_t stream);
+/* out [3][H][W] f32 = u8 / 255 of one U8_HWC or U8_CHW image (crowd.py:144 / to_tensor): the resize branch's input.
+ * EBC_E_ARG: NULL src / out, H or W <= 0, another layout, src or out not 4-byte aligned, 3 H W past int32. */
+int ebc_u8_to_chw01(const void* src, int layout, int H, int W, float* out, ebc_stream_t stream);
+/* ebc_tile_assemble's arithmetic for every image, into maps + map_off, from preds [tiles][Cp][wh/r][ww/r] of the
+ * whole list; counts[i] = the sum of image i's map, added in a fixed order (no atomics: two calls give the same
+ * bits). */
+int ebc_tiles_assemble_batch(const float* preds, const EbcEvalImage* desc, const EbcEvalImage* desc_host, int n_images,
+                             int Cp, int wh, int ww, int sh, int sw, int reduction, float* maps, float* counts,
+                             ebc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training-crop augmentation on device (the reference runs it on CPU in
  * DataLoader workers, utils/data_utils.py:14-26).  One descriptor per output crop (device array);
