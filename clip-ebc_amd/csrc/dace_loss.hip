@@ -74,7 +74,31 @@ template <int G> struct Cfg {
     static constexpr int CW = G < 12 ? G : 12;
     static constexpr int PER_POINT_C = 2 * CW + 6;
     static constexpr size_t FIXED_BYTES_C = (size_t)(5 * GG + 64 + BKT + GG) * 4;
+    // 16 lanes per 4x4 block exist only where every block then still gets its lanes in one pass of the workgroup
+    static constexpr bool W16 = NBK * 16 <= NT;
 };
+
+// The plan of one crop: what the launch puts into Params, what crop_body branches on, and what ebc_dace_plan
+// reports all come from these functions.
+struct Caps { int lds_cap, lds_cap_s, lds_cap_c, w16; };
+template <int G> constexpr Caps caps_of() {
+    using C = Cfg<G>;
+    return Caps{(int)((LDS_MAX - C::FIXED_BYTES) / (sizeof(float) * C::PER_POINT)),
+                (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT)),
+                (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT_C)), C::W16 ? 1 : 0};
+}
+enum { PATH_BUCKET_FULL = 0, PATH_BUCKET_COMPACT = 1, PATH_DENSE_LDS = 2, PATH_DENSE_WS = 3 };
+// the three capacity tests crop_body branches on, and the lane-width test of the bucketed path
+__host__ __device__ __forceinline__ bool fits_full_rows(int n, int lds_cap_s) { return n <= lds_cap_s; }
+__host__ __device__ __forceinline__ bool fits_compact_rows(int n, int lds_cap_c) { return n <= lds_cap_c; }
+__host__ __device__ __forceinline__ bool fits_dense_lds(int n, int lds_cap) { return n <= lds_cap; }
+__host__ __device__ __forceinline__ bool takes_16_lanes(int n, bool w16) { return w16 && n >= SORTED_W16_MIN_POINTS; }
+// the same tests in crop_body's order, for the host-side plan
+inline int dense_path(int n, int lds_cap) { return fits_dense_lds(n, lds_cap) ? PATH_DENSE_LDS : PATH_DENSE_WS; }
+inline int first_path(int n, const Caps& c) {
+    return fits_full_rows(n, c.lds_cap_s) ? PATH_BUCKET_FULL : fits_compact_rows(n, c.lds_cap_c) ? PATH_BUCKET_COMPACT
+                                                                                                 : dense_path(n, c.lds_cap);
+}
 
 // first cell of a point's compact factor row (window start lo, length len; 0 for an empty window)
 template <int G, int CW>
@@ -120,7 +144,8 @@ __device__ __forceinline__ float pcoord(float p, int size, int norm) {
 // underflows beyond ~32 px for reg = 10, i.e. <= 9 grid rows/columns): both products run over
 // [ylo, ylo+ylen) x [xlo, xlo+xlen) only.  Skipping exact zeros leaves every value unchanged up to
 // summation order; the windows are read off the computed factors, so any reg works.
-// Accumulation uses LDS float atomics (order-nondeterministic at the ~1e-7 relative level).
+// K^T u sums per-thread-group LDS partials in a fixed order (no atomics), so a crop's result does not depend on
+// which other crops share the launch.
 __device__ __forceinline__ int block_max(int v, int* scratch) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
 #pragma unroll
@@ -903,8 +928,8 @@ __device__ void crop_body(const Params& P, int b, float* lds)
                 float* spts = reinterpret_cast<float*>(key + n);
                 // 16 lanes per 4x4 block for crops with many points (r02, tools/loss_probe.py: 600 points 883 -> 743 us,
                 // 1000 points 1278 -> 950 us per 16-crop launch; the bench's light crops ran slower on it)
-                constexpr bool W16 = C::NBK * 16 <= NT;
-                const bool ok = (W16 && n >= SORTED_W16_MIN_POINTS)
+                constexpr bool W16 = C::W16;
+                const bool ok = takes_16_lanes(n, W16)
                     ? sinkhorn_sorted<G, CW, W16 ? 16 : 8>(n, P.g, P.size, P.red, P.norm_cood, P.reg, P.max_iter, P.stop_thr,
                                                            P.eval_freq, pts, Ey, Ex, u0, u1, win, key, spts, bkt, bb, v0, v1,
                                                            part, misc, &iters, &rolled, &err_last)
@@ -917,10 +942,10 @@ __device__ void crop_body(const Params& P, int b, float* lds)
                 return true;
             };
             bool done = false;
-            if (n <= P.lds_cap_s) done = bucketed(std::integral_constant<int, G>{});
-            else if (n <= P.lds_cap_c) done = bucketed(std::integral_constant<int, C::CW>{});
+            if (fits_full_rows(n, P.lds_cap_s)) done = bucketed(std::integral_constant<int, G>{});
+            else if (fits_compact_rows(n, P.lds_cap_c)) done = bucketed(std::integral_constant<int, C::CW>{});
             if (!done) {
-                if (n <= P.lds_cap) dense(fac, std::true_type{});
+                if (fits_dense_lds(n, P.lds_cap)) dense(fac, std::true_type{});
                 else dense(P.ws_factors + (size_t)C::PER_POINT * p0, std::false_type{});
             }
         } else {
@@ -987,11 +1012,9 @@ __global__ void dace_finalize_kernel(const float* stats, int B, int count_mode, 
 
 template <int G> int launch(const Params& P0, hipStream_t st)
 {
-    using C = Cfg<G>;
     Params P = P0;
-    P.lds_cap = (int)((LDS_MAX - C::FIXED_BYTES) / (sizeof(float) * C::PER_POINT));
-    P.lds_cap_s = (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT));
-    P.lds_cap_c = (int)((LDS_MAX - C::FIXED_BYTES_C) / (sizeof(float) * C::PER_POINT_C));
+    constexpr Caps caps = caps_of<G>();
+    P.lds_cap = caps.lds_cap; P.lds_cap_s = caps.lds_cap_s; P.lds_cap_c = caps.lds_cap_c;
     if (!ensure_lds<dace_loss_kernel<G>>(LDS_MAX, st)) return EBC_E_LAUNCH;
     {
         const ProbeScope probe(EBC_PROBE_DACE, P.count_mode, 0, 0, 0, P.B, P.total_points, G, st);
@@ -1015,6 +1038,38 @@ extern "C" size_t ebc_dace_workspace_bytes(int B, int total_points, int size, in
 {
     const int G = reduction > 0 ? lds_grid(size / reduction) : 0;
     return sizeof(float) * ((size_t)(2 * (G ? G : 64) + 6) * (size_t)(total_points > 0 ? total_points : 1)) + 256;
+}
+
+// the capacities of LDS grid G (an instantiated size)
+static Caps grid_caps(int G)
+{
+    switch (G) {
+        case 8: return caps_of<8>();
+        case 16: return caps_of<16>();
+        case 24: return caps_of<24>();
+        case 28: return caps_of<28>();
+        case 32: return caps_of<32>();
+        case 40: return caps_of<40>();
+        case 48: return caps_of<48>();
+        case 56: return caps_of<56>();
+        default: return caps_of<64>();
+    }
+}
+
+extern "C" int ebc_dace_plan(int size, int reduction, int n, int* out)
+{
+    if (reduction <= 0 || size <= 0 || size % reduction != 0 || n < 0) return 0;
+    const int G = lds_grid(size / reduction);
+    if (!G) return 0;
+    if (out) {
+        const Caps c = grid_caps(G);
+        const int first = first_path(n, c);
+        out[0] = first;
+        out[1] = first <= PATH_BUCKET_COMPACT ? (takes_16_lanes(n, c.w16 != 0) ? 16 : 8) : 0;
+        out[2] = dense_path(n, c.lds_cap);
+        out[3] = c.lds_cap_s; out[4] = c.lds_cap_c; out[5] = c.lds_cap;
+    }
+    return G;
 }
 
 namespace {
@@ -1059,7 +1114,20 @@ int dace_loss_impl(const float* pred_class, const float* pred_density, const flo
     const int G = lds_grid(g);
     if (g <= 0 || !G) return EBC_E_UNSUPPORTED;                 // density grids up to 64 x 64 (LDS-resident state)
     P.g = g;
-    P.total_points = (int)((workspace_bytes - 256) / (sizeof(float) * (2 * (size_t)G + 6)));
+    if (host_meta) {
+        // the offsets are known here: a crop that can reach the global factor rows (directly, or as the dense
+        // fallback of the bucketed path: either way n > lds_cap) needs the whole workspace
+        const int lds_cap = grid_caps(G).lds_cap;
+        bool needs_ws = false;
+        for (int i = 0; i < B; ++i) {
+            const int n = offsets[i + 1] - offsets[i];
+            if (n < 0) return EBC_E_ARG;
+            needs_ws |= dense_path(n, lds_cap) == PATH_DENSE_WS;
+        }
+        if (needs_ws && (!workspace || workspace_bytes < ebc_dace_workspace_bytes(B, offsets[B], size, reduction)))
+            return EBC_E_ARG;
+    }
+    P.total_points = workspace_bytes >= 256 ? (int)((workspace_bytes - 256) / (sizeof(float) * (2 * (size_t)G + 6))) : 0;
     int rc;
     switch (G) {
         case 8: rc = launch<8>(P, st); break;

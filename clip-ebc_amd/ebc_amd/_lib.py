@@ -98,6 +98,7 @@ class EbcTextGrads(ctypes.Structure):
 SIGNATURES = {
     "ebc_version": (_I, []),
     "ebc_dace_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "ebc_dace_plan": (_I, [_I, _I, _I, _P]),
     "ebc_scale2": (_I, [_P, _P, _P, _L, _P, _P, _L, _P]),
     "ebc_dace_loss_h": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, _I,
                              _P, _P, _P, _P, _P, _P, _P, _Z, _P]),

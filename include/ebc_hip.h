@@ -59,9 +59,26 @@ int ebc_version(void);
  * G in {8,16,24,28,32,40,48,56,64} >= g whose extra cells are dead); EBC_E_UNSUPPORTED above 64.
  * grid cell k sits at k * reduction + reduction / 2 (dm_loss.py:31).
  * norm_cood: OTLoss norm_cood (dm_loss.py:31-34,51): coordinates mapped to [-1, 1].
- * workspace: ebc_dace_workspace_bytes(...) bytes of device memory.
+ * workspace: ebc_dace_workspace_bytes(B, offsets[B], size, reduction) bytes of device memory.  A crop with more
+ *   points than fit LDS (ebc_dace_plan's dense path 3) keeps its (2G + 6) * n_b factor floats there, at float
+ *   offset (2G + 6) * offsets[b].  ebc_dace_loss_h knows the offsets and returns EBC_E_ARG, before any device work,
+ *   when some crop can reach that path and workspace is NULL or workspace_bytes is below that size (and when the
+ *   offsets decrease).  ebc_dace_loss cannot check it, its offsets being device memory: there a NULL or short
+ *   workspace with such a crop is the caller's out-of-bounds write.  Crops that stay in LDS never touch it.
  */
 size_t ebc_dace_workspace_bytes(int B, int total_points, int size, int reduction);
+/* The plan the fused loss runs for one crop of n points at this geometry (host-only, no device work; computed by
+ * the functions the launch and the kernel branch on): returns the LDS grid G in {8,16,24,28,32,40,48,56,64}, or 0
+ * when the geometry is unsupported (reduction <= 0, size not a positive multiple of it, size / reduction > 64,
+ * n < 0), and writes out[6] (out may be NULL):
+ *   out[0]  the Sinkhorn path tried first: 0 bucketed with full factor rows, 1 bucketed with compact 12-cell rows,
+ *           2 dense in LDS, 3 dense from the workspace (a crop with n = 0 runs no Sinkhorn at all);
+ *   out[1]  lanes per 4x4 cell block of the bucketed path (8 or 16), 0 when out[0] is dense;
+ *   out[2]  the dense path (2 or 3) taken when the bucketed one refuses the crop (a factor window wider than 9
+ *           cells), and by out[0] >= 2 itself;
+ *   out[3]  lds_cap_s: most points of path 0;  out[4]  lds_cap_c: most points of path 1 (equal to lds_cap_s where
+ *           compact rows are no shorter, G = 8);  out[5]  lds_cap: most points of path 2. */
+int ebc_dace_plan(int size, int reduction, int n, int* out);
 /* a_out[i] = a[i] * *s, b_out[i] = b[i] * *s (s a device scalar): the loss gradients times the upstream gradient of the
  * loss (GradScaler's scale) in one launch */
 int ebc_scale2(const float* s, const float* a, float* a_out, long na, const float* b, float* b_out, long nb,

@@ -281,3 +281,63 @@ def test_product_has_no_cpu_fallback():
     from ebc_amd import _lib
     with pytest.raises(RuntimeError):
         _lib.lib()
+
+
+# ------------------------------------------------------------------------------------------- fused DACE loss: plan
+# ebc_dace_plan per LDS grid at reduction 8: (size, G, lds_cap_s, lds_cap_c, lds_cap, 16 lanes offered)
+DACE_PLAN = [(64, 8, 1840, 1840, 1471, True), (128, 16, 1034, 1310, 826, True), (192, 24, 691, 1245, 553, True),
+             (224, 28, 582, 1202, 468, True), (256, 32, 494, 1154, 392, True), (320, 40, 361, 1036, 287, False),
+             (384, 48, 262, 892, 217, False), (448, 56, 183, 722, 157, False), (512, 64, 117, 526, 87, False)]
+
+
+def _plan(lib, size, red, n):
+    import ctypes
+    out = (ctypes.c_int * 6)()
+    return lib.ebc_dace_plan(size, red, n, out), list(out)
+
+
+@pytest.mark.parametrize("size,G,cap_s,cap_c,cap,w16", DACE_PLAN)
+def test_dace_plan_table(lib, size, G, cap_s, cap_c, cap, w16):
+    """The capacities are the recorded ones (a capacity one point too high would put a crop's last factor row past the
+    LDS allocation), and the paths switch exactly at them."""
+    for n in (0, 1, 17, 256, 257, cap, cap + 1, cap_s, cap_s + 1, cap_c, cap_c + 1, 5000):
+        g, out = _plan(lib, size, 8, n)
+        assert g == G and out[3:] == [cap_s, cap_c, cap], (n, g, out)
+        first = 0 if n <= cap_s else 1 if n <= cap_c else (2 if n <= cap else 3)
+        assert out[0] == first and out[2] == (2 if n <= cap else 3), (n, out)
+        assert out[1] == (0 if first >= 2 else 16 if (w16 and n >= 257) else 8), (n, out)
+    assert cap <= cap_s <= cap_c
+    for pad in range(size - 8, max(size - 32, 0), -8):          # a padded density grid runs on the same LDS grid
+        if all(pad // 8 > t[1] for t in DACE_PLAN if t[1] < G):
+            assert _plan(lib, pad, 8, 1)[0] == G, pad
+
+
+def test_dace_plan_geometry(lib):
+    assert lib.ebc_dace_plan(8, 8, 1, None) == 8 and lib.ebc_dace_plan(24, 8, 1, None) == 8
+    assert lib.ebc_dace_plan(320, 16, 1, None) == 24 and lib.ebc_dace_plan(640, 16, 1, None) == 40
+    assert lib.ebc_dace_plan(768, 32, 1, None) == 24 and lib.ebc_dace_plan(512, 16, 1, None) == 32
+    for bad in ((520, 8, 1), (224, 0, 1), (224, -8, 1), (225, 8, 1), (0, 8, 1), (224, 8, -1)):
+        assert lib.ebc_dace_plan(*bad, None) == 0, bad
+
+
+def _dace_h(lib, offsets, size, ws, ws_bytes, red=8):
+    """ebc_dace_loss_h with every argument valid but, possibly, the offsets and the workspace; no pointer is read
+    before the checks under test."""
+    import ctypes
+    B = len(offsets) - 1
+    o = (ctypes.c_int * (B + 1))(*offsets)
+    return lib.ebc_dace_loss_h(_X, _X, _X, 0, _X, o, None, _X, _X, B, 5, size, red, 0, 0, 1.0, 0.1, 0.01, 10.0, 100, 1e-9,
+                               10, _X, _X, _X, _X, None, None, ws, ws_bytes, None)
+
+
+@pytest.mark.parametrize("size,G,cap_s,cap_c,cap,w16", DACE_PLAN)
+def test_dace_loss_h_refuses_a_missing_or_short_workspace(lib, size, G, cap_s, cap_c, cap, w16):
+    """Return codes only, all before any launch: a crop that can reach the workspace path (more than lds_cap points:
+    directly, or as the dense fallback of the bucketed path) needs the whole workspace."""
+    for offsets in ([0, 3, 3 + cap + 1], [0, cap_c + 1], [0, 0, cap_s + 1, cap_s + 2]):
+        need = lib.ebc_dace_workspace_bytes(len(offsets) - 1, offsets[-1], size, 8)
+        assert _dace_h(lib, offsets, size, None, need) == EBC_E_ARG
+        assert _dace_h(lib, offsets, size, None, 0) == EBC_E_ARG
+        for short in (0, 8, 255, 256, need - 1):
+            assert _dace_h(lib, offsets, size, _X, short) == EBC_E_ARG, (offsets, short)
+    assert _dace_h(lib, [0, 5, 3], size, _X, 1 << 24) == EBC_E_ARG          # offsets that decrease
