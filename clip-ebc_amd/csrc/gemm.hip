@@ -866,7 +866,8 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLW)) void gemm_nt_kernel(GemmArg
                 // LN: W'.1 of the lane's columns; each row's rstd and rstd * mean from its partials in LDS (stage_stats):
                 // the row's 4 lanes read 16-B pairs q = fg, fg + 4 and meet by lane swaps, so every tile of a row sums in
                 // the same order (same bits).  var = E[x^2] - mean^2 in f32 (|mean| / std <= 0.15 on the encoder's rows;
-                // tests/test_gpu_model.py holds the error to the LayerNorm-launch path's)
+                // tests/test_gpu_vit_stages.py holds mean / rstd per row to float64 with the cancellation term
+                // c u E[x^2] / (var + eps), tests/_vit_refs.py fold_stat_bounds, also on rows with |mean| / std ~ 3)
                 float lw[LN && NP > 0 ? NP : 1][8], lwo[4];
                 float rsv[LN ? TM : 1], rsmuv[LN ? TM : 1];
                 if constexpr (LN) {

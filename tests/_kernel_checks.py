@@ -1,5 +1,5 @@
 """Helpers shared by the per-kernel GPU modules (test_gpu_bn_kernels.py, test_gpu_encoder_kernels.py,
-test_gpu_gemm_kernels.py, test_gpu_conv_kernels.py): sentinel-guarded
+test_gpu_gemm_kernels.py, test_gpu_conv_kernels.py, test_gpu_vit_stages.py): sentinel-guarded
 output buffers, operand lifetime, and the per-element checks that print "RATIO <name> <largest error / bound>" before
 they assert."""
 import torch
