@@ -341,3 +341,50 @@ def test_dace_loss_h_refuses_a_missing_or_short_workspace(lib, size, G, cap_s, c
         for short in (0, 8, 255, 256, need - 1):
             assert _dace_h(lib, offsets, size, _X, short) == EBC_E_ARG, (offsets, short)
     assert _dace_h(lib, [0, 5, 3], size, _X, 1 << 24) == EBC_E_ARG          # offsets that decrease
+
+
+# ------------------------------------------------------------------------------------------- Sinkhorn, Adam: host side
+def test_sinkhorn_workspace_bytes_is_host_only(lib):
+    """0 for a non-positive size, 0 while K fits LDS beside u, v and K^T u (199 x 199), the whole of K from 200 x 200."""
+    for na, nb in ((0, 5), (5, 0), (-1, 5), (5, -7), (0, 0)):
+        assert lib.ebc_sinkhorn_workspace_bytes(na, nb) == 0
+    assert lib.ebc_sinkhorn_workspace_bytes(199, 199) == 0
+    assert lib.ebc_sinkhorn_workspace_bytes(200, 200) == 4 * 200 * 200
+
+
+def _sinkhorn(lib, a=_X, b=_X, C=_X, na=8, nb=8, reg=0.5, max_iter=1, thr=1e-9, eval_freq=10, info=_X, ws=None, wsb=0):
+    return lib.ebc_sinkhorn(a, b, C, na, nb, reg, max_iter, thr, eval_freq, 1, _X, _X, _X, _X, _X, _X, info, ws, wsb, None)
+
+
+@pytest.mark.parametrize("kw", [dict(reg=0.0), dict(reg=-1.0), dict(reg=float("nan")), dict(eval_freq=0), dict(eval_freq=-3),
+                                dict(info=None), dict(a=None), dict(b=None), dict(C=None), dict(na=0), dict(nb=-2),
+                                dict(na=200, nb=200), dict(na=200, nb=200, ws=_X, wsb=4 * 200 * 200 - 1)])
+def test_sinkhorn_rejects_without_device(lib, kw):
+    """reg <= 0, eval_freq <= 0, a NULL info or operand, an empty shape, a workspace shape without its workspace."""
+    assert _sinkhorn(lib, **kw) == EBC_E_ARG
+
+
+def test_sinkhorn_oversize_is_unsupported_without_device(lib):
+    """u, v and K^T u must stay in LDS: nb = 13632 at na = 1 is the first size that does not fit."""
+    assert _sinkhorn(lib, na=1, nb=13632, ws=_X, wsb=1 << 30) == EBC_E_UNSUPPORTED
+    assert _sinkhorn(lib, na=1, nb=13633, ws=_X, wsb=1 << 30) == EBC_E_UNSUPPORTED
+    assert _sinkhorn(lib, na=20000, nb=20000, ws=_X, wsb=1 << 40) == EBC_E_UNSUPPORTED
+
+
+def _adam(lib, fn, tensors=_X, n=1, step=_X, spar=0, scaler=_X, cpar=0, interval=2000):
+    if fn == "check":
+        return lib.ebc_amp_check(tensors, n, scaler, cpar, None)
+    f = lib.ebc_adam_step if fn == "step" else lib.ebc_adam_update
+    return f(tensors, n, step, spar, scaler, cpar, 1e-3, 0.9, 0.999, 1e-8, 0.0, 2.0, 0.5, interval, 1, None)
+
+
+_ADAM_BAD = [dict(n=0), dict(n=-1), dict(tensors=None), dict(cpar=2), dict(cpar=-1)]
+_ADAM_BAD_UPDATE = [dict(spar=2), dict(spar=-1), dict(step=None), dict(interval=0), dict(interval=-5)]
+
+
+@pytest.mark.parametrize("fn,kw", [(fn, kw) for fn in ("step", "update") for kw in _ADAM_BAD + _ADAM_BAD_UPDATE] +
+                         [("check", kw) for kw in _ADAM_BAD + [dict(scaler=None)]])
+def test_adam_rejects_without_device(lib, fn, kw):
+    """n <= 0, NULL tensors, a parity that is neither 0 nor 1, growth_interval <= 0, a NULL step count; the check alone
+    also refuses a NULL scaler (the two update calls take it as "no scaler")."""
+    assert _adam(lib, fn, **kw) == EBC_E_ARG
