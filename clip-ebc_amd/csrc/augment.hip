@@ -13,6 +13,7 @@
 //
 // Launches per batch of crops (all crops of all images in each launch, RB-row blocks):
 //   resize_h: rows of each crop window -> [3][crop_h][out_w] scratch (horizontal AA-bicubic taps)
+//             (resize_h_raw: the same from stored uint8 HWC / CHW or f32 CHW sources, rows staged in LDS)
 //   resize_v: scratch -> [3][out_h][out_w] output (vertical taps), horizontal flip on the store
 //   gray_partial, pointwise, blur_v, blur_h: the per-crop op lists (see pointwise_kernel)
 // Byte work (HBM/L2-bound): every thread owns output columns, so all loads/stores are row-contiguous.
@@ -68,6 +69,128 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const float* __restrict__
             tmp[(size_t)r * d.out_w + ox] = acc;
         }
     }
+}
+
+// ---- the horizontal pass from stored images (uint8 HWC / CHW, f32 CHW): resize_h_kernel's arithmetic, the source
+// rows staged in LDS.  A workgroup owns RB rows of one crop (of one plane; of all three for HWC, whose bytes are
+// interleaved) and one chunk of output columns whose input span fits a staged row.
+constexpr int RAW_ROW_BYTES = 4096;                    // span bytes of one staged row
+constexpr int RAW_LDW = RAW_ROW_BYTES / 4 + 1;         // + the up to 3 bytes in front of an unaligned row start
+// RB rows of RAW_LDW dwords + the 256-entry u/255 table = 17.0 KiB: nine workgroups a CU by LDS, eight by waves
+
+__host__ __device__ inline int raw_cap_px(int layout) {
+    return layout == EBC_EVAL_U8_HWC ? RAW_ROW_BYTES / 3 : layout == EBC_EVAL_U8_CHW ? RAW_ROW_BYTES : RAW_ROW_BYTES / 4;
+}
+// output columns per chunk.  With S = ceil(crop_w / out_w) >= scale the input span of oc columns is at most
+// scale (oc - 1) + 2 support + 1 + rounding <= S oc + 3 S + 2 pixels (support <= 2 S), which this keeps <= the cap;
+// integer arithmetic, so the host's grid and the kernel agree
+__host__ __device__ inline int raw_chunk_cols(int layout, int crop_w, int out_w) {
+    const int S = (crop_w + out_w - 1) / out_w;
+    const int oc = (raw_cap_px(layout) - 2 - 4 * S) / S;
+    return oc < 1 ? 1 : (oc > out_w ? out_w : oc);
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ void resize_h_raw_body(const uint8_t* __restrict__ src, const EbcCropSrc& s, const EbcCropDesc& d,
+                                                  int c, int r0, int chunk, float* __restrict__ ws,
+                                                  uint32_t (*lds)[RAW_LDW], const float* lut)
+{
+    constexpr bool F32 = LAYOUT == EBC_EVAL_F32_CHW;
+    constexpr int NC = LAYOUT == EBC_EVAL_U8_HWC ? 3 : 1;          // channels a workgroup owns = bytes per pixel step
+    const int tid = threadIdx.x;
+    const int oc = raw_chunk_cols(LAYOUT, d.crop_w, d.out_w);
+    const int ox0 = chunk * oc;
+    if (ox0 >= d.out_w) return;
+    const int ox1 = min(ox0 + oc, d.out_w);
+    const Taps tf = aa_taps(ox0, d.crop_w, d.out_w), tl = aa_taps(ox1 - 1, d.crop_w, d.out_w);
+    const int lo0 = tf.lo, span = tl.lo + tl.n - lo0;              // input columns [lo0, lo0 + span) of the window
+    // a single column's taps wider than a staged row (a > 250-fold reduction): read the source directly
+    const bool staged = span <= raw_cap_px(LAYOUT);
+    const int nr = min(RB, d.crop_h - r0);
+    const uint8_t* row[RB];                                        // first needed byte of each row
+    int sh[RB];                                                    // its offset from the aligned dword below it
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+        const int y = d.top + r0 + min(r, nr - 1);
+        const size_t px = LAYOUT == EBC_EVAL_U8_HWC ? ((size_t)y * s.W + d.left + lo0) * 3
+                                                    : ((size_t)c * s.H + y) * s.W + d.left + lo0;
+        row[r] = src + s.src_off + px * (F32 ? 4 : 1);
+        sh[r] = F32 ? 0 : (int)(reinterpret_cast<uintptr_t>(row[r]) & 3);
+    }
+    if (staged) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            if (r >= nr) continue;
+            if (F32) {
+                const uint32_t* g = reinterpret_cast<const uint32_t*>(row[r]);
+                for (int i = tid; i < span; i += 256) lds[r][i] = g[i];
+            } else {
+                // bytes [s0, end) relative to the aligned address a0: single bytes up to the first dword boundary b0,
+                // whole dwords to the last boundary b1, single bytes after it
+                const int s0 = sh[r], end = s0 + span * NC;
+                const int b0 = (s0 + 3) & ~3, b1 = end & ~3;
+                const uint8_t* a0 = row[r] - s0;                   // (never dereferenced below row[r])
+                const uint32_t* g = reinterpret_cast<const uint32_t*>(a0);
+                uint8_t* l = reinterpret_cast<uint8_t*>(lds[r]);
+                for (int i = (b0 >> 2) + tid; i < (b1 >> 2); i += 256) lds[r][i] = g[i];
+                const int he = min(b0, end), tb = max(b1, b0);
+                if (s0 + tid < he) l[s0 + tid] = a0[s0 + tid];
+                if (tb + tid < end) l[tb + tid] = a0[tb + tid];
+            }
+        }
+        __syncthreads();
+    }
+    for (int ox = ox0 + tid; ox < ox1; ox += 256) {
+        const Taps t = aa_taps(ox, d.crop_w, d.out_w);
+        const int rel = t.lo - lo0;
+        float acc[RB][NC];
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+#pragma unroll
+            for (int cc = 0; cc < NC; ++cc) acc[r][cc] = 0.f;
+        for (int j = 0; j < t.n; ++j) {
+            const float w = tap_w(t, j);
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                if (r >= nr) continue;
+#pragma unroll
+                for (int cc = 0; cc < NC; ++cc) {
+                    float px;
+                    if (F32) {
+                        px = staged ? __uint_as_float(lds[r][rel + j]) : reinterpret_cast<const float*>(row[r])[rel + j];
+                    } else {
+                        const int b = (rel + j) * NC + cc;
+                        px = lut[staged ? reinterpret_cast<const uint8_t*>(lds[r])[sh[r] + b] : row[r][b]];
+                    }
+                    acc[r][cc] = fmaf(w, px, acc[r][cc]);
+                }
+            }
+        }
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) {
+            float* tmp = ws + d.tmp_off + (size_t)(c + cc) * d.crop_h * d.out_w;
+#pragma unroll
+            for (int r = 0; r < RB; ++r)
+                if (r < nr) tmp[(size_t)(r0 + r) * d.out_w + ox] = acc[r][cc];
+        }
+    }
+}
+
+// grid (row blocks of the tallest crop, 3 n, column chunks of the crop with the most)
+__global__ __launch_bounds__(256) void resize_h_raw_kernel(const uint8_t* __restrict__ src, const EbcCropSrc* __restrict__ csrc,
+                                                           const EbcCropDesc* __restrict__ desc, float* __restrict__ ws)
+{
+    __shared__ uint32_t lds[RB][RAW_LDW];
+    __shared__ float lut[256];
+    const int k = blockIdx.y / 3, c = blockIdx.y % 3, r0 = blockIdx.x * RB;
+    const EbcCropSrc s = csrc[k];
+    const EbcCropDesc d = desc[k];
+    if (r0 >= d.crop_h || (s.layout == EBC_EVAL_U8_HWC && c != 0)) return;
+    lut[threadIdx.x] = (float)threadIdx.x / 255.0f;                // the conversion, one correctly rounded division each
+    __syncthreads();
+    if (s.layout == EBC_EVAL_U8_HWC) resize_h_raw_body<EBC_EVAL_U8_HWC>(src, s, d, 0, r0, blockIdx.z, ws, lds, lut);
+    else if (s.layout == EBC_EVAL_U8_CHW) resize_h_raw_body<EBC_EVAL_U8_CHW>(src, s, d, c, r0, blockIdx.z, ws, lds, lut);
+    else resize_h_raw_body<EBC_EVAL_F32_CHW>(src, s, d, c, r0, blockIdx.z, ws, lds, lut);
 }
 
 __global__ __launch_bounds__(256) void resize_v_kernel(const EbcCropDesc* __restrict__ desc, const float* __restrict__ ws,
@@ -307,6 +430,22 @@ __global__ void point_map_kernel(const float* __restrict__ pts, const int* __res
 
 }  // namespace
 
+// the per-crop op lists on the resized crops: gray_partial, pointwise, blur_v, blur_h
+static int launch_crop_ops(const EbcCropDesc* desc, int n, int max_out_h, float* out, float* workspace, const float* noise,
+                           EbcAugConst k, hipStream_t st)
+{
+    const int nb = (max_out_h + RB - 1) / RB;
+    hipLaunchKernelGGL(gray_partial_kernel, dim3(nb, n), dim3(PT), 0, st, desc, out, workspace);
+    EBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pointwise_kernel, dim3(nb, n), dim3(PT), 0, st, desc, out, workspace, noise, k);
+    EBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(blur_v_kernel, dim3(nb, 3 * n), dim3(PT), 0, st, desc, out, workspace, k);
+    EBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(blur_h_kernel, dim3(nb, 3 * n), dim3(PT), 0, st, desc, out, workspace, noise, k);
+    EBC_CHECK_LAUNCH();
+    return EBC_OK;
+}
+
 extern "C" int ebc_augment_crops(const float* src, const EbcCropDesc* desc, int n, int max_crop_h, int max_out_h,
                                  float* out, float* workspace, const float* noise, EbcAugConst k, ebc_stream_t stream)
 {
@@ -320,16 +459,40 @@ extern "C" int ebc_augment_crops(const float* src, const EbcCropDesc* desc, int 
         hipLaunchKernelGGL(resize_v_kernel, dim3((max_out_h + RB - 1) / RB, 3 * n), dim3(256), 0, st, desc, workspace, out);
         EBC_CHECK_LAUNCH();
     }
-    const int nb = (max_out_h + RB - 1) / RB;
-    hipLaunchKernelGGL(gray_partial_kernel, dim3(nb, n), dim3(PT), 0, st, desc, out, workspace);
+    return launch_crop_ops(desc, n, max_out_h, out, workspace, noise, k, st);
+}
+
+extern "C" int ebc_augment_crops_raw(const void* src, const EbcCropSrc* csrc, const EbcCropSrc* csrc_host,
+                                     const EbcCropDesc* desc, const EbcCropDesc* desc_host, int n, float* out,
+                                     float* workspace, const float* noise, EbcAugConst k, ebc_stream_t stream)
+{
+    constexpr long long I32 = 0x7FFFFFFFll;
+    if (!src || !csrc || !csrc_host || !desc || !desc_host || !out || !workspace || n < 0 || 3ll * n > 65535) return EBC_E_ARG;
+    if (k.blur_k < 1 || k.blur_k > EBC_AUG_MAX_BLUR || (k.blur_k & 1) == 0) return EBC_E_ARG;
+    int max_crop_h = 0, max_out_h = 0, max_chunks = 1;
+    for (int i = 0; i < n; ++i) {
+        const EbcCropSrc& s = csrc_host[i];
+        const EbcCropDesc& d = desc_host[i];
+        if (s.layout != EBC_EVAL_U8_HWC && s.layout != EBC_EVAL_U8_CHW && s.layout != EBC_EVAL_F32_CHW) return EBC_E_ARG;
+        if (s.src_off < 0 || s.H <= 0 || s.W <= 0 || 3ll * s.H * s.W > I32) return EBC_E_ARG;
+        if (s.layout == EBC_EVAL_F32_CHW && ((s.src_off & 3) || (reinterpret_cast<uintptr_t>(src) & 3))) return EBC_E_ARG;
+        if (d.crop_h <= 0 || d.crop_w <= 0 || d.out_h <= 0 || d.out_w <= 0 || d.top < 0 || d.left < 0) return EBC_E_ARG;
+        if ((long long)d.top + d.crop_h > s.H || (long long)d.left + d.crop_w > s.W) return EBC_E_ARG;
+        if (3ll * d.crop_h * d.out_w > I32 || 3ll * d.out_h * d.out_w > I32) return EBC_E_ARG;
+        const int oc = raw_chunk_cols(s.layout, d.crop_w, d.out_w), chunks = (d.out_w + oc - 1) / oc;
+        if (chunks > 65535) return EBC_E_ARG;
+        max_crop_h = d.crop_h > max_crop_h ? d.crop_h : max_crop_h;
+        max_out_h = d.out_h > max_out_h ? d.out_h : max_out_h;
+        max_chunks = chunks > max_chunks ? chunks : max_chunks;
+    }
+    if (n == 0) return EBC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(resize_h_raw_kernel, dim3((max_crop_h + RB - 1) / RB, 3 * n, max_chunks), dim3(256), 0, st,
+                       (const uint8_t*)src, csrc, desc, workspace);
     EBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pointwise_kernel, dim3(nb, n), dim3(PT), 0, st, desc, out, workspace, noise, k);
+    hipLaunchKernelGGL(resize_v_kernel, dim3((max_out_h + RB - 1) / RB, 3 * n), dim3(256), 0, st, desc, workspace, out);
     EBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(blur_v_kernel, dim3(nb, 3 * n), dim3(PT), 0, st, desc, out, workspace, k);
-    EBC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(blur_h_kernel, dim3(nb, 3 * n), dim3(PT), 0, st, desc, out, workspace, noise, k);
-    EBC_CHECK_LAUNCH();
-    return EBC_OK;
+    return launch_crop_ops(desc, n, max_out_h, out, workspace, noise, k, st);
 }
 
 extern "C" int ebc_point_map(const float* points, const int* offsets, int B, int H, int W, int max_points, float* out,

@@ -51,6 +51,12 @@ class EbcEvalImage(ctypes.Structure):
                 ("layout", ctypes.c_int32)]
 
 
+class EbcCropSrc(ctypes.Structure):
+    """include/ebc_hip.h EbcCropSrc (the stored source of one crop of ebc_augment_crops_raw)."""
+    _fields_ = [("src_off", ctypes.c_int64), ("layout", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class EbcProbeRecord(ctypes.Structure):
     """include/ebc_hip.h EbcProbeRecord (one instrumented launch)."""
     _fields_ = [(n, ctypes.c_int) for n in ("kind", "epi", "bm", "bn", "mode", "m", "n", "k")] + [("ms", ctypes.c_float)]
@@ -172,6 +178,7 @@ SIGNATURES = {
     "ebc_bn_add_relu_flat": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "ebc_prep_weights_1x1": (_I, [_I, _P, _P, _P, _I, _I, _P]),
     "ebc_augment_crops": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, EbcAugConst, _P]),
+    "ebc_augment_crops_raw": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, EbcAugConst, _P]),
     "ebc_point_map": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ebc_adam_step": (_I, [_P, _I, _P, _I, _P, _I, _D, _D, _D, _D, _D, _D, _D, _I, _I, _P]),
     "ebc_amp_check": (_I, [_P, _I, _P, _I, _P]),

@@ -23,6 +23,7 @@ import torch.distributed as dist
 from torch import Tensor, nn
 
 from . import _lib
+from ._raw import _raw_image
 from .distributed import gather_shards, shard_range
 from .transforms import IMAGENET_MEAN, IMAGENET_STD, _upload
 
@@ -135,19 +136,6 @@ def fit_size(H: int, W: int, window, stride, fit: Optional[str] = None) -> Tuple
         return (int(max(round((H - window[0]) / strd[0]), 0) * strd[0] + window[0]),
                 int(max(round((W - window[1]) / strd[1]), 0) * strd[1] + window[1]))
     raise ValueError(f"fit must be one of {FITS}, got {fit!r}")
-
-
-def _raw_image(img) -> Tuple[Tensor, int, int, int]:
-    """A uint8 [H,W,3] or [3,H,W] image -> (contiguous tensor, layout code, H, W)."""
-    if not isinstance(img, Tensor):
-        img = torch.as_tensor(img)
-    if img.dtype != torch.uint8 or img.dim() != 3 or 3 not in (img.shape[0], img.shape[-1]):
-        raise ValueError(f"images must be uint8 [H,W,3] or [3,H,W], got {img.dtype} {tuple(img.shape)}")
-    if img.shape[0] == 3 and img.shape[-1] == 3:
-        raise ValueError(f"cannot tell [H,W,3] from [3,H,W] for an image of shape {tuple(img.shape)}")
-    if img.shape[-1] == 3:
-        return img.contiguous(), _lib.EBC_EVAL_U8_HWC, int(img.shape[0]), int(img.shape[1])
-    return img.contiguous(), _lib.EBC_EVAL_U8_CHW, int(img.shape[1]), int(img.shape[2])
 
 
 def _align16(n: int) -> int:

@@ -9,6 +9,14 @@ arithmetic), and the pixel work of a whole batch runs in three launches (`ebc_au
 crop + antialiased-bicubic resize, flip, colour jitter, blur, salt-and-pepper, normalise) plus one for
 the dot maps (`ebc_point_map`).
 
+Sources: an image is a [3, H, W] float32 tensor in [0, 1] on the device, or the image as it is stored -- uint8
+[H, W, 3] (a decoded JPEG) or [3, H, W] (the reference's .npy files, datasets/crowd.py:141-148) -- on the device (read
+in place) or on the CPU (only the crop windows are packed, `pack_crop_windows`, and uploaded in one copy).  A batch of
+float32 device images runs `ebc_augment_crops` as before; any stored image in it makes it `ebc_augment_crops_raw`,
+whose horizontal pass reads bytes (rows staged in LDS, `(float)u / 255.0f`, the float pass's taps and fmaf chain): the
+crops are bit-equal to the float path's on `u8.float() / 255`, the RNG draws and the label arithmetic are untouched.
+`ebc_amd.loader.RawCropLoader` yields a train split's batches this way.
+
 Surface (mirrors the reference):
   * `CropAugment(...)` -- the train-split `Compose([RandomResizedCrop, RandomHorizontalFlip,
     RandomApply([ColorJitter, GaussianBlur, PepperSaltNoise])])` of `get_dataloader`
@@ -33,12 +41,13 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _lib
+from ._raw import _raw_image
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)   # datasets/crowd.py:64
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -97,6 +106,71 @@ def _upload(descs, dev) -> Tensor:
     pinned block alive until the copy has run)."""
     host = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).pin_memory()
     return host.to(dev, non_blocking=True)
+
+
+def _is_f32_device(t) -> bool:
+    return isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
+class PackedWindows(NamedTuple):
+    """What `pack_crop_windows` packed: per plan the stored source its crop reads from `buffer` (offset -1: the
+    plan's image is not a CPU uint8 image and nothing was packed for it)."""
+    buffer: Tensor                 # uint8, CPU; the first `nbytes` bytes are the packing
+    nbytes: int
+    offsets: List[int]             # byte offset of the plan's source in the buffer, 16-byte aligned
+    layouts: List[int]             # _lib.EBC_EVAL_U8_HWC / _lib.EBC_EVAL_U8_CHW
+    heights: List[int]             # stored height of the source: crop_h of a window, H of a whole image
+    widths: List[int]              # stored row length in pixels: crop_w of a window, W of a whole image
+
+
+def pack_crop_windows(plans: Sequence[CropPlan], images: Sequence, out: Optional[Tensor] = None,
+                      pin: bool = False) -> PackedWindows:
+    """Gather what `plans` read of the CPU uint8 images into one byte buffer (host only: neither the library nor a
+    device is touched, and no float image is made).
+
+    A plan's window is `crop_h` rows of `3 * crop_w` bytes for an [H,W,3] image and three planes of `crop_h x crop_w`
+    bytes for a [3,H,W] one; a `pre_resize` plan needs its whole (small) image, packed once per image.  Every source
+    starts on a multiple of 16 bytes.  Entries of `images` that are not CPU uint8 tensors are skipped.  `out`: a uint8
+    CPU buffer to fill if it is large enough (a pinned one of the loader's); otherwise one is allocated (`pin`)."""
+    raws: Dict[int, Tuple[Tensor, int, int, int]] = {}
+    whole: Dict[int, int] = {}
+    offsets, layouts, heights, widths = [], [], [], []
+    total = 0
+    for p in plans:
+        img = images[p.image]
+        if isinstance(img, Tensor) and (img.is_cuda or img.dtype != torch.uint8):
+            offsets.append(-1), layouts.append(-1), heights.append(0), widths.append(0)
+            continue
+        if p.image not in raws:
+            raws[p.image] = _raw_image(img)
+        _, layout, H, W = raws[p.image]
+        if p.pre_resize is not None:
+            if p.image not in whole:
+                whole[p.image] = total
+                total = (total + 3 * H * W + 15) & ~15
+            off, h, w = whole[p.image], H, W
+        else:
+            if p.top < 0 or p.left < 0 or p.top + p.crop_h > H or p.left + p.crop_w > W or p.crop_h <= 0 or p.crop_w <= 0:
+                raise ValueError(f"crop window outside its image: {p}")
+            off, h, w = total, p.crop_h, p.crop_w
+            total = (total + 3 * h * w + 15) & ~15
+        offsets.append(off), layouts.append(layout), heights.append(h), widths.append(w)
+    if out is not None and out.numel() >= total:
+        buf = out
+    else:
+        buf = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=pin)
+    done = set()
+    for p, off, layout, h, w in zip(plans, offsets, layouts, heights, widths):
+        if off < 0 or off in done:
+            continue
+        done.add(off)
+        t = raws[p.image][0]
+        top, left = (0, 0) if p.pre_resize is not None else (p.top, p.left)
+        if layout == _lib.EBC_EVAL_U8_HWC:
+            buf[off:off + 3 * h * w].view(h, w, 3).copy_(t[top:top + h, left:left + w, :])
+        else:
+            buf[off:off + 3 * h * w].view(3, h, w).copy_(t[:, top:top + h, left:left + w])
+    return PackedWindows(buf, total, offsets, layouts, heights, widths)
 
 
 class CropAugment:
@@ -190,8 +264,138 @@ class CropAugment:
         return plan, label
 
     # ---------------------------------------------------------------- device half
-    def apply(self, images: Sequence[Tensor], plans: Sequence[CropPlan], normalize: bool = True) -> Tensor:
-        """Run the pixel work of `plans` on `images` ([3, H, W] f32 in [0, 1] on the device)."""
+    def apply(self, images: Sequence[Tensor], plans: Sequence[CropPlan], normalize: bool = True,
+              windows: Optional[Tuple[PackedWindows, Tensor]] = None) -> Tensor:
+        """Run the pixel work of `plans` on `images`: per image a [3, H, W] f32 tensor in [0, 1] on the device, or the
+        image as it is stored -- uint8 [H, W, 3] or [3, H, W], on the device (read in place) or on the CPU (only the
+        plans' windows are packed and uploaded, in one copy).  `windows`: the packing of `pack_crop_windows(plans,
+        images)` and its copy on the device, when the caller has uploaded it already (RawCropLoader's prefetch)."""
+        if windows is None and all(_is_f32_device(t) for t in images):
+            return self._apply_f32(images, plans, normalize)
+        return self._apply_raw(images, plans, normalize, windows)
+
+    def _fill_ops(self, d, k: int, p: CropPlan, normalize: bool, fields: list) -> None:
+        """Everything of crop k's descriptor but its source and its scratch offset."""
+        out_h, out_w = self.size
+        d.out_off = k * 3 * out_h * out_w
+        d.top, d.left, d.crop_h, d.crop_w, d.out_h, d.out_w = p.top, p.left, p.crop_h, p.crop_w, out_h, out_w
+        d.flip = int(p.flip)
+        ops, f = 0, {JIT_BRIGHTNESS: 1.0, JIT_CONTRAST: 1.0, JIT_SATURATION: 1.0, JIT_HUE: 0.0}
+        for slot, (op, v) in enumerate(p.jitter):
+            ops |= op << (3 * slot)
+            f[op] = v
+        d.jitter_ops = ops
+        d.brightness, d.contrast, d.saturation = f[JIT_BRIGHTNESS], f[JIT_CONTRAST], f[JIT_SATURATION]
+        d.hue = f[JIT_HUE]
+        d.blur, d.noise = int(p.blur), int(p.noise)
+        d.saltiness, d.spiciness, d.seed = self.saltiness, self.spiciness, p.seed & 0xFFFFFFFF
+        d.noise_off = -1
+        if p.noise and p.noise_field is not None:
+            if tuple(p.noise_field.shape) != (3, out_h, out_w) or p.noise_field.dtype != torch.float32:
+                raise ValueError(f"noise_field must be float32 [3, {out_h}, {out_w}], got {p.noise_field.shape}")
+            d.noise_off = len(fields) * 3 * out_h * out_w
+            fields.append(p.noise_field)
+        d.normalize = int(normalize)
+
+    def _apply_raw(self, images: Sequence, plans: Sequence[CropPlan], normalize: bool,
+                   windows: Optional[Tuple[PackedWindows, Tensor]]) -> Tensor:
+        """`apply` with at least one stored (uint8) image: `ebc_augment_crops_raw`, one source descriptor per crop."""
+        L = _lib.lib()
+        out_h, out_w = self.size
+        n = len(plans)
+        # per image: (device tensor or None, layout, H, W)
+        srcs = []
+        for t in images:
+            if _is_f32_device(t):
+                if not (t.is_contiguous() and t.dim() == 3 and t.shape[0] == 3):
+                    raise ValueError("images must be contiguous [3, H, W] float32 device tensors")
+                srcs.append((t, _lib.EBC_EVAL_F32_CHW, int(t.shape[1]), int(t.shape[2])))
+            elif isinstance(t, Tensor) and t.dtype != torch.uint8:
+                raise ValueError("images must be [3, H, W] float32 device tensors or uint8 [H,W,3] / [3,H,W] tensors")
+            else:
+                r, layout, H, W = _raw_image(t)
+                srcs.append((r if r.is_cuda else None, layout, H, W))
+        on_dev = [s[0].device for s in srcs if s[0] is not None]
+        if windows is not None:
+            dev = windows[1].device
+        else:
+            dev = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty(n, 3, out_h, out_w, device=dev)
+        if n == 0:
+            return out
+        with _lib.on(dev):
+            st = _lib.stream(dev)
+            if windows is None and any(s[0] is None for s in srcs):
+                packed = pack_crop_windows(plans, images, pin=True)
+                windows = (packed, packed.buffer[:max(packed.nbytes, 16)].to(dev, non_blocking=True))
+            packed, dwin = windows if windows is not None else (None, None)
+
+            def stored(k: int, p: CropPlan):
+                """(address, layout, H, W) of what plan k's image is stored as on the device."""
+                t, layout, H, W = srcs[p.image]
+                if t is not None:
+                    return t.data_ptr(), layout, H, W
+                if packed.offsets[k] < 0:
+                    raise ValueError(f"no packed window for plan {k}")
+                return dwin.data_ptr() + packed.offsets[k], packed.layouts[k], packed.heights[k], packed.widths[k]
+
+            # whole-image pre-resizes (RandomResizedCrop's small-image branch) first, as their own crops into f32 planes
+            pre = [k for k, p in enumerate(plans) if p.pre_resize is not None]
+            pre_off, pre_buf = {}, None
+            if pre:
+                total = 0
+                for k in pre:
+                    pre_off[k] = total
+                    total += 3 * plans[k].pre_resize[0] * plans[k].pre_resize[1]
+                pre_buf = torch.empty(total, device=dev)
+                addr = [stored(k, plans[k]) for k in pre]
+                base = min(a[0] for a in addr) & ~3
+                cs, ds = (_lib.EbcCropSrc * len(pre))(), (_lib.EbcCropDesc * len(pre))()
+                tmp = 0
+                for i, k in enumerate(pre):
+                    a, layout, H, W = addr[i]
+                    h, w = plans[k].pre_resize
+                    cs[i].src_off, cs[i].layout, cs[i].H, cs[i].W = a - base, layout, H, W
+                    d = ds[i]
+                    d.out_off, d.tmp_off, d.noise_off = pre_off[k], tmp, -1
+                    d.top, d.left, d.crop_h, d.crop_w, d.out_h, d.out_w = 0, 0, H, W, h, w
+                    tmp += 3 * max(H, h) * w
+                ws = torch.empty(tmp, device=dev)
+                dcs, dds = _upload(cs, dev), _upload(ds, dev)
+                _lib.check(L.ebc_augment_crops_raw(ctypes.c_void_p(base), _lib.ptr(dcs), cs, _lib.ptr(dds), ds, len(pre),
+                                                   _lib.ptr(pre_buf), _lib.ptr(ws), None, self.const, st),
+                           "ebc_augment_crops_raw (pre-resize)")
+            addr = []
+            for k, p in enumerate(plans):
+                if k in pre_off:
+                    addr.append((pre_buf.data_ptr() + 4 * pre_off[k], _lib.EBC_EVAL_F32_CHW, p.pre_resize[0], p.pre_resize[1]))
+                else:
+                    addr.append(stored(k, p))
+            base = min(a[0] for a in addr) & ~3
+            cs, ds = (_lib.EbcCropSrc * n)(), (_lib.EbcCropDesc * n)()
+            tmp, fields = 0, []
+            for k, p in enumerate(plans):
+                a, layout, H, W = addr[k]
+                cs[k].src_off, cs[k].layout, cs[k].H, cs[k].W = a - base, layout, H, W
+                d = ds[k]
+                self._fill_ops(d, k, p, normalize, fields)
+                d.tmp_off = tmp
+                if k not in pre_off and srcs[p.image][0] is None:        # a packed window is its own source
+                    d.top = d.left = 0
+                if d.top + d.crop_h > H or d.left + d.crop_w > W or d.top < 0 or d.left < 0:
+                    raise ValueError(f"crop window outside its image: {p}")
+                tmp += 3 * max(p.crop_h, out_h) * out_w
+            ws = torch.empty(tmp, device=dev)
+            dcs, dds = _upload(cs, dev), _upload(ds, dev)
+            noise = None
+            if fields:
+                noise = torch.stack(fields).pin_memory().to(dev, non_blocking=True)
+            _lib.check(L.ebc_augment_crops_raw(ctypes.c_void_p(base), _lib.ptr(dcs), cs, _lib.ptr(dds), ds, n, _lib.ptr(out),
+                                               _lib.ptr(ws), _lib.ptr(noise), self.const, st), "ebc_augment_crops_raw")
+        return out     # temporaries are released stream-ordered (caching allocator), after the launches
+
+    def _apply_f32(self, images: Sequence[Tensor], plans: Sequence[CropPlan], normalize: bool = True) -> Tensor:
+        """`apply` on [3, H, W] f32 device images: `ebc_augment_crops`."""
         L = _lib.lib()
         dev = images[0].device
         out_h, out_w = self.size
@@ -225,28 +429,11 @@ class CropAugment:
             off = src.data_ptr() - base
             assert off % 4 == 0
             d = descs[k]
-            d.src_off, d.out_off, d.tmp_off = off // 4, k * 3 * out_h * out_w, tmp
+            self._fill_ops(d, k, p, normalize, fields)
+            d.src_off, d.tmp_off = off // 4, tmp
             d.src_h, d.src_w = src.shape[1], src.shape[2]
-            d.top, d.left, d.crop_h, d.crop_w, d.out_h, d.out_w = p.top, p.left, p.crop_h, p.crop_w, out_h, out_w
             if p.top + p.crop_h > d.src_h or p.left + p.crop_w > d.src_w or p.top < 0 or p.left < 0:
                 raise ValueError(f"crop window outside its image: {p}")
-            d.flip = int(p.flip)
-            ops, f = 0, {JIT_BRIGHTNESS: 1.0, JIT_CONTRAST: 1.0, JIT_SATURATION: 1.0, JIT_HUE: 0.0}
-            for slot, (op, v) in enumerate(p.jitter):
-                ops |= op << (3 * slot)
-                f[op] = v
-            d.jitter_ops = ops
-            d.brightness, d.contrast, d.saturation = f[JIT_BRIGHTNESS], f[JIT_CONTRAST], f[JIT_SATURATION]
-            d.hue = f[JIT_HUE]
-            d.blur, d.noise = int(p.blur), int(p.noise)
-            d.saltiness, d.spiciness, d.seed = self.saltiness, self.spiciness, p.seed & 0xFFFFFFFF
-            d.noise_off = -1
-            if p.noise and p.noise_field is not None:
-                if tuple(p.noise_field.shape) != (3, out_h, out_w) or p.noise_field.dtype != torch.float32:
-                    raise ValueError(f"noise_field must be float32 [3, {out_h}, {out_w}], got {p.noise_field.shape}")
-                d.noise_off = len(fields) * 3 * out_h * out_w
-                fields.append(p.noise_field)
-            d.normalize = int(normalize)
             tmp += 3 * max(p.crop_h, out_h) * out_w
             max_ch = max(max_ch, p.crop_h)
         ws = torch.empty(tmp, device=dev)
@@ -279,13 +466,21 @@ class CropAugment:
         """Crowd.__getitem__ for each image (num_crops crops) + collate_fn: (images, points, densities)."""
         plans, points = [], []
         for i, (img, lab) in enumerate(zip(images, labels)):
+            in_h, in_w = image_size(img)
             for _ in range(num_crops):
-                p, l = self.plan_crop(i, img.shape[-2], img.shape[-1], lab.clone().float())
+                p, l = self.plan_crop(i, in_h, in_w, lab.clone().float())
                 plans.append(p)
                 points.append(l)
         imgs = self.apply(images, plans)
         dens = generate_density_map(points, self.size[0], self.size[1], device=imgs.device)
         return imgs, points, dens
+
+
+def image_size(img) -> Tuple[int, int]:
+    """(H, W) of a [3, H, W] float image or of a stored uint8 [H, W, 3] / [3, H, W] one."""
+    if isinstance(img, Tensor) and img.dtype != torch.uint8:
+        return int(img.shape[-2]), int(img.shape[-1])
+    return _raw_image(img)[2:]
 
 
 def generate_density_map(points: Sequence[Tensor], height: int, width: int, device=None) -> Tensor:

@@ -466,6 +466,31 @@ typedef struct {
 /* max_crop_h / max_out_h: maxima over the descriptors (grid sizing) */
 int ebc_augment_crops(const float* src, const EbcCropDesc* desc, int n, int max_crop_h, int max_out_h, float* out,
                       float* workspace, const float* noise, EbcAugConst k, ebc_stream_t stream);
+/* ebc_augment_crops from stored images as they are: the same six launches, but the horizontal pass reads crop i's
+ * window through csrc[i] -- uint8 [H][W][3] (a decoded JPEG) or [3][H][W] (the reference's .npy images,
+ * datasets/crowd.py:141-148), or f32 [3][H][W] in [0, 1] (a pre-resized image) -- with the layout codes of
+ * EbcEvalImage; one launch may mix the three.  A uint8 sample is (float)u / 255.0f (crowd.py:144), every output value
+ * the float pass's fmaf chain over the float pass's taps, so the result is bit-equal to ebc_augment_crops on
+ * u8.float() / 255.  desc[i].top / left / crop_h / crop_w address the stored source; src_off, src_h and src_w of
+ * EbcCropDesc are unused.  A workgroup stages the byte spans of its rows in LDS (aligned dwords for the body, single
+ * bytes for head and tail: no byte outside the window's rows is read, so a source may end on the last byte of its
+ * allocation) and windows wider than the staging rows are processed in column chunks.
+ * Both arrays are taken twice, on the device (what the kernels read) and on the host (what the checks and the grid
+ * sizes read; only read during the call).
+ * EBC_E_ARG, before any device work: NULL src / csrc / desc (either copy) / out / workspace, n < 0 or n > 21845, a
+ * layout that is none of the three, src_off < 0, an F32_CHW source whose src_off or src is not 4-byte aligned, H or W
+ * <= 0, a window that leaves its source (top < 0, left < 0, top + crop_h > H, left + crop_w > W), crop_h / crop_w /
+ * out_h / out_w <= 0, blur_k as ebc_augment_crops, and any size past int32 (3 H W of a source, 3 crop_h out_w,
+ * 3 out_h out_w). */
+typedef struct {
+    int64_t src_off;                     /* byte offset of the stored source in src */
+    int32_t layout;                      /* EBC_EVAL_U8_HWC / EBC_EVAL_U8_CHW / EBC_EVAL_F32_CHW */
+    int32_t H, W;                        /* stored height and row length, in pixels */
+    int32_t reserved;
+} EbcCropSrc;
+int ebc_augment_crops_raw(const void* src, const EbcCropSrc* csrc, const EbcCropSrc* csrc_host, const EbcCropDesc* desc,
+                          const EbcCropDesc* desc_host, int n, float* out, float* workspace, const float* noise,
+                          EbcAugConst k, ebc_stream_t stream);
 /* generate_density_map(label, H, W, sigma=None) (datasets/utils.py:11-28) for B crops: out [B][1][H][W]
  * = 1 at (clamp(int y), clamp(int x)) of points [sum n, 2] (x, y), offsets [B+1] (device) */
 int ebc_point_map(const float* points, const int* offsets, int B, int H, int W, int max_points, float* out,
