@@ -122,6 +122,11 @@ size_t head_bwd_text_ws_bytes(int P, int NB, int embed);
 int head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
                   const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
                   int embed, void* ws, size_t wsb, hipStream_t st);
+// the same for up to 32 bins: the text rows pass through LDS in groups (partials carry 32 dot slots)
+size_t head_bwd_text_wide_ws_bytes(int P, int NB, int embed);
+int head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                       const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                       int embed, void* ws, size_t wsb, hipStream_t st);
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st);
 int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, hipStream_t st,
                   const TouchList* touch = nullptr);

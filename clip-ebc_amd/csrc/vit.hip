@@ -451,6 +451,20 @@ extern "C" int ebc_head_bwd_text(int dtype_z, const void* Z, const float* text, 
     return ebc::head_bwd_text(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, embed,
                               workspace, workspace_bytes, (hipStream_t)stream);
 }
+extern "C" size_t ebc_head_bwd_text_wide_workspace_bytes(int P, int NB, int embed)
+{
+    return ebc::head_bwd_text_wide_ws_bytes(P, NB, embed);
+}
+extern "C" int ebc_head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale,
+                                      const float* anchors, const float* dlogits, const float* dexp, const float* gscale,
+                                      float* dtext, int P, int HW, int NB, int embed, void* workspace,
+                                      size_t workspace_bytes, ebc_stream_t stream)
+{
+    if (!Z || !text || !logit_scale || !anchors || !dlogits || !dexp || !dtext) return EBC_E_ARG;
+    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
+    return ebc::head_bwd_text_wide(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, embed,
+                                   workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" int ebc_im2col(int dtype, const float* x, void* out, int B, int H, int W, int patch, ebc_stream_t stream)
 {
     if (!x || !out || B <= 0 || patch <= 0 || H < patch || W < patch) return EBC_E_ARG;

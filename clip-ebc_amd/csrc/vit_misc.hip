@@ -330,7 +330,9 @@ __global__ __launch_bounds__(256) void vpt_grad_kernel(float* __restrict__ dX, T
 }
 
 // ----------------------------------------------------------------------------- similarity head
-// One wave per pixel, CH channels (CH / 64 per lane, in float4 pieces 256 apart), NB <= 16 bins; the text
+// One wave per pixel, CH channels (CH / 64 per lane, in float4 pieces 256 apart), NB <= CAP bins (CAP = the capacity of
+// the per-pixel register arrays: 16, or 32 = EBC_HEAD_MAX_BINS for 17 .. 32 bins; the launchers pick the instance by
+// NB, so a call with NB <= 16 runs the CAP = 16 instance it always ran); the text
 // features are normalised in LDS.  CH = 512 (ViT-B/16) or 1024 (ResNet-50, models/clip/model.py:85-95).
 // pixels per 4-wave block (r02, tools/kbench.py head): the forward is fastest with one pixel per wave (4: 15.7 us vs
 // 18.5 at 16, 16 crops); the backward with 8 per wave (32: 38.2 vs 42.2 us; fewer blocks also mean fewer d bias
@@ -383,7 +385,7 @@ __device__ __forceinline__ float text_dot(const float* t, const float* zs) {
     return d;
 }
 
-template <class TZ, int CH>
+template <class TZ, int CH, int CAP = 16>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const TZ* __restrict__ Z, const float* text, const float* logit_scale,
                                                        const float* anchors, float* logits, float* expo, int P, int HW, int NB)
 {
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const TZ* __restrict__ Z,
         float zs[NV];
 #pragma unroll
         for (int j = 0; j < NV; ++j) zs[j] = s * (v[j] * inv);
-        float lg[16];
+        float lg[CAP];
         float mx = -INFINITY;
         for (int k = 0; k < NB; ++k) {
             lg[k] = wave_sum(text_dot<CH>(tn + k * CH, zs));
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const TZ* __restrict__ Z,
 // also this block's d bias (column sums of its dZ rows) and d logit_scale partial: part[block][0..CH) and
 // part[block][CH] (plain stores; head_bias_finalize_kernel sums the blocks in order -- bit-reproducible, where float
 // atomics from every block into the same CH addresses were neither reproducible nor free of contention).
-template <class TZ, class TD, int CH>
+template <class TZ, class TD, int CH, int CAP = 16>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const TZ* __restrict__ Z, const float* text, const float* logit_scale,
                                                        const float* anchors, const float* dlogits, const float* dexp,
                                                        const float* gscale, TD* dZ, float* part, int P, int HW, int NB)
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const TZ* __restrict__ Z,
         float zn[NV], zs[NV];
 #pragma unroll
         for (int j = 0; j < NV; ++j) { zn[j] = v[j] * inv; zs[j] = s * zn[j]; }
-        float lg[16], pr[16];
+        float lg[CAP], pr[CAP];
         float mx = -INFINITY;
         for (int k = 0; k < NB; ++k) {
             lg[k] = wave_sum(text_dot<CH>(tn + k * CH, zs));
@@ -563,8 +565,9 @@ constexpr int HEAD_TXT_PPB = 64;
 template <int CH>
 constexpr int head_txt_kb() { return CH <= 512 ? 16 : 8; }
 
-// floats of one workgroup's partial: [NB][CH] sums, then the bins' dot slots padded to 16 (rows stay float4-aligned)
-__host__ __device__ inline size_t head_txt_stride(int NB, int CH) { return (size_t)NB * CH + 16; }
+// floats of one workgroup's partial: [NB][CH] sums, then the bins' dot slots padded to 16 (rows stay float4-aligned);
+// 32 slots in the wide kernel's partials
+__host__ __device__ inline size_t head_txt_stride(int NB, int CH, int pad = 16) { return (size_t)NB * CH + pad; }
 
 template <class TZ, int CH>
 __global__ __launch_bounds__(256) void head_text_bwd_kernel(const TZ* __restrict__ Z, const float* text, const float* logit_scale,
@@ -686,7 +689,7 @@ __global__ __launch_bounds__(256) void head_text_bwd_kernel(const TZ* __restrict
 // dtext[k][c] from the blocks' partials: workgroup (x, k) sums columns 64 x .. 64 x + 63 of bin k and the bin's dot slot
 // over the blocks exactly as head_bias_finalize_kernel does (8 waves x 8 interleaved chains, combined in a fixed order),
 // then wave 0 applies exp(ls) and the F.normalize backward of text row k
-template <int CH>
+template <int CH, int PAD = 16>
 __global__ __launch_bounds__(512) void head_text_finalize_kernel(const float* __restrict__ part, int nblk, int NB,
                                                                  const float* __restrict__ text, const float* logit_scale,
                                                                  float* __restrict__ dtext)
@@ -695,7 +698,7 @@ __global__ __launch_bounds__(512) void head_text_finalize_kernel(const float* __
     __shared__ float wd[8];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int k = blockIdx.y, c = blockIdx.x * 64 + lane;
-    const size_t stride = head_txt_stride(NB, CH);
+    const size_t stride = head_txt_stride(NB, CH, PAD);
     const float* pc = part + (size_t)k * CH + c;
     const float* pd = part + (size_t)NB * CH + k;
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -724,6 +727,167 @@ __global__ __launch_bounds__(512) void head_text_finalize_kernel(const float* __
         const float dtn = expf(*logit_scale) * t;
         dtext[(size_t)k * CH + c] = (nrm > 1e-12f ? dtn - (tk[c] * inv) * dot : dtn) * inv;
     }
+}
+
+// ---- d text for up to 32 bins (ebc_head_bwd_text_wide).  With 32 rows the layout above needs 32 x 1024 x 4 = 128 KiB
+// of text rows plus 32 KiB of wave sums plus the dl slots: over a CU's 160 KiB.  So the normalised rows pass through a
+// 64 KiB LDS window in groups of RG = 16384 / CH rows (32 at 512 channels: one group; 16 at 1024: two), and the work
+// splits into three phases over the workgroup's 64 pixels (Z is re-read from L2 in each, 2 - 4 KB a pixel):
+//   1. per group: every wave's pixels x the group's rows -> logits into lg_l (LDS), 1 / ||z|| into inv_l
+//   2. per pixel: all NB logits from lg_l into registers, softmax / expectation / dl as head_bwd_kernel forms them;
+//      dl overwrites the logits in lg_l, dl x logit accumulates into the bins' dot sums
+//   3. per KB bins: sum_p dl[p][k] zn_p in KB x NV accumulators a lane, the four waves combined in wave order, exactly
+//      as head_text_bwd_kernel's later passes
+// Partials: [NB][CH] sums then 32 dot slots a workgroup; head_text_finalize_kernel<CH, 32> sums them in its fixed order.
+// LDS: (min(NB, RG) + KB) x CH x 4 + 8.75 KiB: at most 104.75 KiB at either width, one workgroup a CU.
+constexpr int HEAD_MAX_BINS = 32;
+
+template <int CH>
+constexpr int head_txtw_rows() { return 16384 / CH; }
+
+template <class TZ, int CH>
+__global__ __launch_bounds__(256) void head_text_wide_bwd_kernel(const TZ* __restrict__ Z, const float* text,
+                                                                 const float* logit_scale, const float* anchors,
+                                                                 const float* dlogits, const float* dexp, const float* gscale,
+                                                                 float* __restrict__ part, int P, int HW, int NB)
+{
+    constexpr int NV = CH / 64, KB = head_txt_kb<CH>(), PPW = HEAD_TXT_PPB / 4, G = 32 / NV, RG = head_txtw_rows<CH>();
+    constexpr int CAP = HEAD_MAX_BINS;
+    extern __shared__ __attribute__((aligned(16))) float tn[];   // [min(NB, RG)][CH]: one group of normalised rows
+    float* red = tn + min(NB, RG) * CH;     // [KB][CH]: the waves' sums, combined in wave order
+    float* lg_l = red + KB * CH;            // [4 waves][PPW][CAP]: logits (phase 1), then dl
+    float* inv_l = lg_l + 4 * PPW * CAP;    // [4][PPW]
+    float* dot_l = inv_l + 4 * PPW;         // [4][CAP]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float s = expf(*logit_scale);
+    const float gs = gscale ? *gscale : 1.0f;
+    float* pblk = part + (size_t)blockIdx.x * head_txt_stride(NB, CH, CAP);
+    // phase 1: logits
+    for (int r0 = 0; r0 < NB; r0 += RG) {
+        const int nr = min(RG, NB - r0);
+        if (r0) __syncthreads();            // every wave is done with the previous group
+        load_text<CH>(text + (size_t)r0 * CH, nr, tn);
+        for (int i0 = 0; i0 < PPW; i0 += G) {
+            const int p0 = blockIdx.x * HEAD_TXT_PPB + w + 4 * i0;
+            if (p0 >= P) break;
+            float vv[G][NV];
+#pragma unroll
+            for (int g = 0; g < G; ++g) load_pix<TZ, CH>(Z + (size_t)min(p0 + 4 * g, P - 1) * CH, vv[g]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int p = p0 + 4 * g, i = i0 + g;
+                if (p >= P) continue;
+                float* v = vv[g];
+                float ss = 0.f;
+#pragma unroll
+                for (int j = 0; j < NV; ++j) ss += v[j] * v[j];
+                const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+                float zs[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) zs[j] = s * (v[j] * inv);
+                for (int kk = 0; kk < nr; ++kk) {
+                    const float l = wave_sum(text_dot<CH>(tn + kk * CH, zs));
+                    if (lane == 0) lg_l[(w * PPW + i) * CAP + r0 + kk] = l;
+                }
+                if (r0 == 0 && lane == 0) inv_l[w * PPW + i] = inv;
+            }
+        }
+    }
+    __syncthreads();
+    // phase 2: dl of the wave's own pixels (every lane computes the same values, as in head_text_bwd_kernel)
+    float dots[CAP];
+#pragma unroll
+    for (int k = 0; k < CAP; ++k) dots[k] = 0.f;
+    for (int i = 0; i < PPW; ++i) {
+        const int p = blockIdx.x * HEAD_TXT_PPB + w + 4 * i;
+        if (p >= P) break;
+        float* row = lg_l + (w * PPW + i) * CAP;
+        float lg[CAP], pr[CAP];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) {
+            lg[k] = k < NB ? row[k] : -INFINITY;
+            mx = fmaxf(mx, lg[k]);
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) { pr[k] = k < NB ? expf(lg[k] - mx) : 0.f; if (k < NB) se += pr[k]; }
+        float e = 0.f;
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) if (k < NB) { pr[k] /= se; e += pr[k] * anchors[k]; }
+        const int b = p / HW, hw = p % HW;
+        const float de = dexp[(size_t)b * HW + hw] * gs;
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) {
+            if (k >= NB) continue;
+            // d logit_k, as in head_bwd_kernel
+            const float dl = dlogits[((size_t)b * NB + k) * HW + hw] * gs + de * pr[k] * (anchors[k] - e);
+            dots[k] += dl * lg[k];
+            if (lane == 0) row[k] = dl;
+        }
+    }
+    __syncthreads();
+    // phase 3: sum_p dl[p][k] zn_p, KB bins a pass
+    for (int k0 = 0; k0 < NB; k0 += KB) {
+        float acc[KB][NV];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+            for (int j = 0; j < NV; ++j) acc[kk][j] = 0.f;
+        for (int i0 = 0; i0 < PPW; i0 += G) {
+            const int p0 = blockIdx.x * HEAD_TXT_PPB + w + 4 * i0;
+            if (p0 >= P) break;
+            float vv[G][NV];
+#pragma unroll
+            for (int g = 0; g < G; ++g) load_pix<TZ, CH>(Z + (size_t)min(p0 + 4 * g, P - 1) * CH, vv[g]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int p = p0 + 4 * g, i = i0 + g;
+                if (p >= P) continue;
+                const float inv = inv_l[w * PPW + i];
+                float dlr[KB];
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) dlr[kk] = k0 + kk < NB ? lg_l[(w * PPW + i) * CAP + k0 + kk] : 0.f;
+                float zn[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) zn[j] = vv[g][j] * inv;
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) {
+                    if (k0 + kk >= NB) continue;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) acc[kk][j] += dlr[kk] * zn[j];
+                }
+            }
+        }
+        // ((wave 0 + wave 1) + wave 2) + wave 3, the last one straight to the block's partial rows
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            if (w == ww) {
+#pragma unroll
+                for (int kk = 0; kk < KB; ++kk) {
+                    if (k0 + kk >= NB) continue;
+#pragma unroll
+                    for (int q = 0; q < NV / 4; ++q) {
+                        float4 a = make_float4(acc[kk][4 * q], acc[kk][4 * q + 1], acc[kk][4 * q + 2], acc[kk][4 * q + 3]);
+                        float4* r = reinterpret_cast<float4*>(red + kk * CH + 256 * q + 4 * lane);
+                        if (ww > 0) { const float4 o = *r; a.x = o.x + a.x; a.y = o.y + a.y; a.z = o.z + a.z; a.w = o.w + a.w; }
+                        if (ww < 3) *r = a;
+                        else *reinterpret_cast<float4*>(pblk + (size_t)(k0 + kk) * CH + 256 * q + 4 * lane) = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // lane 0's dots are the wave's per-pixel sums (wave_sum results are lane-uniform)
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < CAP; ++k) dot_l[w * CAP + k] = dots[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < CAP)
+        pblk[(size_t)NB * CH + threadIdx.x] = threadIdx.x < NB ? (dot_l[threadIdx.x] + dot_l[CAP + threadIdx.x]) +
+                                                                  (dot_l[2 * CAP + threadIdx.x] + dot_l[3 * CAP + threadIdx.x]) : 0.f;
 }
 
 template <class T>
@@ -907,6 +1071,15 @@ static int head_fwd_t(int dtype_z, const void* Z, const float* text, const float
 {
     const dim3 grid((P + HEAD_FWD_PPB - 1) / HEAD_FWD_PPB);
     const size_t lds = (size_t)NB * CH * 4;
+    if (NB > 16) {      // 17 .. 32 bins: the 32-slot instance; up to 64 KiB (CH 512) / 128 KiB (CH 1024) of text rows
+        constexpr int LDS_MAX = HEAD_MAX_BINS * CH * 4;
+        EBC_DTYPE_SWITCH(dtype_z,
+            if (!ensure_lds<head_fwd_kernel<T, CH, HEAD_MAX_BINS>>(LDS_MAX, st)) return EBC_E_LAUNCH;
+            hipLaunchKernelGGL((head_fwd_kernel<T, CH, HEAD_MAX_BINS>), grid, dim3(256), lds, st, (const T*)Z, text,
+                               logit_scale, anchors, logits, expo, P, HW, NB));
+        EBC_CHECK_LAUNCH();
+        return EBC_OK;
+    }
     EBC_DTYPE_SWITCH(dtype_z, hipLaunchKernelGGL((head_fwd_kernel<T, CH>), grid, dim3(256), lds, st, (const T*)Z, text,
                                                  logit_scale, anchors, logits, expo, P, HW, NB));
     EBC_CHECK_LAUNCH();
@@ -916,7 +1089,7 @@ static int head_fwd_t(int dtype_z, const void* Z, const float* text, const float
 int head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
              float* logits, float* expo, int P, int HW, int NB, int embed, hipStream_t st)
 {
-    if (NB <= 0 || NB > 16) return EBC_E_UNSUPPORTED;
+    if (NB <= 0 || NB > HEAD_MAX_BINS) return EBC_E_UNSUPPORTED;
     if (embed == 512) return head_fwd_t<512>(dtype_z, Z, text, logit_scale, anchors, logits, expo, P, HW, NB, st);
     if (embed == 1024) return head_fwd_t<1024>(dtype_z, Z, text, logit_scale, anchors, logits, expo, P, HW, NB, st);
     return EBC_E_UNSUPPORTED;
@@ -935,10 +1108,18 @@ static int head_bwd_t(int dtype_z, int dtype_dz, const void* Z, const float* tex
     const size_t lds = ((size_t)NB * CH + 4 * CH + 4) * 4;
     constexpr int LDS_MAX = (16 * CH + 4 * CH + 4) * 4;      // NB <= 16 (embed 1024: 81 KiB)
     // the dZ element type is the caller's buffer type (dtype_dz), independent of Z's
-    EBC_DTYPE_SWITCH(dtype_z, using TZ = T; EBC_DTYPE_SWITCH(dtype_dz,
-        if (!ensure_lds<head_bwd_kernel<TZ, T, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH;
-        hipLaunchKernelGGL((head_bwd_kernel<TZ, T, CH>), grid, dim3(256), lds, st, (const TZ*)Z, text, logit_scale, anchors,
-                           dlogits, dexp, gscale, (T*)dZ, part, P, HW, NB)));
+    if (NB > 16) {      // 17 .. 32 bins: the 32-slot instance (embed 1024: up to 144 KiB, one workgroup a CU)
+        constexpr int LDS_WIDE = (HEAD_MAX_BINS * CH + 4 * CH + 4) * 4;
+        EBC_DTYPE_SWITCH(dtype_z, using TZ = T; EBC_DTYPE_SWITCH(dtype_dz,
+            if (!ensure_lds<head_bwd_kernel<TZ, T, CH, HEAD_MAX_BINS>>(LDS_WIDE, st)) return EBC_E_LAUNCH;
+            hipLaunchKernelGGL((head_bwd_kernel<TZ, T, CH, HEAD_MAX_BINS>), grid, dim3(256), lds, st, (const TZ*)Z, text,
+                               logit_scale, anchors, dlogits, dexp, gscale, (T*)dZ, part, P, HW, NB)));
+    } else {
+        EBC_DTYPE_SWITCH(dtype_z, using TZ = T; EBC_DTYPE_SWITCH(dtype_dz,
+            if (!ensure_lds<head_bwd_kernel<TZ, T, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH;
+            hipLaunchKernelGGL((head_bwd_kernel<TZ, T, CH>), grid, dim3(256), lds, st, (const TZ*)Z, text, logit_scale, anchors,
+                               dlogits, dexp, gscale, (T*)dZ, part, P, HW, NB)));
+    }
     EBC_CHECK_LAUNCH();
     if (sums) {
         hipLaunchKernelGGL(head_bias_finalize_kernel<CH>, dim3(CH / 64 + 1), dim3(512), 0, st, part, nblk, dbias, dscale);
@@ -956,7 +1137,7 @@ int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const 
              const float* dlogits, const float* dexp, const float* gscale, void* dZ, float* dbias, float* dscale,
              int P, int HW, int NB, int embed, void* ws, size_t wsb, hipStream_t st)
 {
-    if (NB <= 0 || NB > 16 || P <= 0) return EBC_E_UNSUPPORTED;
+    if (NB <= 0 || NB > HEAD_MAX_BINS || P <= 0) return EBC_E_UNSUPPORTED;
     if (embed == 512)
         return head_bwd_t<512>(dtype_z, dtype_dz, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dZ, dbias, dscale, P, HW, NB,
                                ws, wsb, st);
@@ -1004,6 +1185,46 @@ int head_bwd_text(int dtype_z, const void* Z, const float* text, const float* lo
     if (embed == 512)
         return head_bwd_text_t<512>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
     return head_bwd_text_t<1024>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
+}
+
+size_t head_bwd_text_wide_ws_bytes(int P, int NB, int embed)
+{
+    if (P <= 0 || NB <= 0 || NB > HEAD_MAX_BINS || (embed != 512 && embed != 1024)) return 0;
+    return (size_t)((P + HEAD_TXT_PPB - 1) / HEAD_TXT_PPB) * head_txt_stride(NB, embed, HEAD_MAX_BINS) * sizeof(float);
+}
+
+template <int CH>
+static int head_bwd_text_wide_t(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                                const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW,
+                                int NB, void* ws, hipStream_t st)
+{
+    constexpr int KB = head_txt_kb<CH>(), PPW = HEAD_TXT_PPB / 4, RG = head_txtw_rows<CH>(), CAP = HEAD_MAX_BINS;
+    const int nblk = (P + HEAD_TXT_PPB - 1) / HEAD_TXT_PPB;
+    float* part = reinterpret_cast<float*>(ws);
+    const size_t lds = ((size_t)(NB < RG ? NB : RG) * CH + KB * CH + 4 * PPW * CAP + 4 * PPW + 4 * CAP) * 4;
+    constexpr int LDS_MAX = (RG * CH + KB * CH + 4 * PPW * CAP + 4 * PPW + 4 * CAP) * 4;      // 104.75 KiB
+    const ProbeScope probe(EBC_PROBE_HEAD_BWD_TEXT, 0, 0, 0, 0, P, NB, CH, st);
+    EBC_DTYPE_SWITCH(dtype_z,
+        if (!ensure_lds<head_text_wide_bwd_kernel<T, CH>>(LDS_MAX, st)) return EBC_E_LAUNCH;
+        hipLaunchKernelGGL((head_text_wide_bwd_kernel<T, CH>), dim3(nblk), dim3(256), lds, st, (const T*)Z, text, logit_scale,
+                           anchors, dlogits, dexp, gscale, part, P, HW, NB));
+    EBC_CHECK_LAUNCH();
+    hipLaunchKernelGGL((head_text_finalize_kernel<CH, CAP>), dim3(CH / 64, NB), dim3(512), 0, st, part, nblk, NB, text,
+                       logit_scale, dtext);
+    EBC_CHECK_LAUNCH();
+    return EBC_OK;
+}
+
+int head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                       const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                       int embed, void* ws, size_t wsb, hipStream_t st)
+{
+    if (NB <= 0 || NB > HEAD_MAX_BINS || (embed != 512 && embed != 1024)) return EBC_E_UNSUPPORTED;
+    if (dtype_z != EBC_F32 && dtype_z != EBC_F16 && dtype_z != EBC_BF16) return EBC_E_ARG;
+    if (!ws || wsb < head_bwd_text_wide_ws_bytes(P, NB, embed)) return EBC_E_ARG;
+    if (embed == 512)
+        return head_bwd_text_wide_t<512>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
+    return head_bwd_text_wide_t<1024>(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, ws, st);
 }
 
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st)

@@ -134,6 +134,8 @@ SIGNATURES = {
     "ebc_head_bwd_workspace_bytes": (_Z, [_I, _I]),
     "ebc_head_bwd_text": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "ebc_head_bwd_text_workspace_bytes": (_Z, [_I, _I, _I]),
+    "ebc_head_bwd_text_wide": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "ebc_head_bwd_text_wide_workspace_bytes": (_Z, [_I, _I, _I]),
     "ebc_cast_f32": (_I, [_I, _P, _P, _Z, _P]),
     "ebc_attention_causal_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _P]),
     "ebc_attention_causal_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

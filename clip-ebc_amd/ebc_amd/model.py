@@ -329,10 +329,12 @@ class _HeadFn(torch.autograd.Function):
         dtext = None
         if ctx.needs_input_grad[4]:                                # a trainable text tower (model.py:201-208)
             dtext = torch.empty(NB, E, device=dev, dtype=torch.float32)
-            wt = _dec_workspace(dev, L.ebc_head_bwd_text_workspace_bytes(P, NB, E), slot=3)
-            _lib.check(L.ebc_head_bwd_text(_lib.EBC_F32, _lib.ptr(Z), _lib.ptr(text), _lib.ptr(ls), _lib.ptr(anchors),
-                                           _lib.ptr(dl), _lib.ptr(de), None, _lib.ptr(dtext), P, HW, NB, E,
-                                           _lib.ptr(wt), wt.numel(), st), "ebc_head_bwd_text")
+            # up to 16 bins: the entry point (and arithmetic) of always; 17 .. 32: the one that streams the text rows
+            name = "ebc_head_bwd_text" if NB <= 16 else "ebc_head_bwd_text_wide"
+            wt = _dec_workspace(dev, getattr(L, name + "_workspace_bytes")(P, NB, E), slot=3)
+            _lib.check(getattr(L, name)(_lib.EBC_F32, _lib.ptr(Z), _lib.ptr(text), _lib.ptr(ls), _lib.ptr(anchors),
+                                        _lib.ptr(dl), _lib.ptr(de), None, _lib.ptr(dtext), P, HW, NB, E,
+                                        _lib.ptr(wt), wt.numel(), st), name)
         return dy, dW, dbias, dscale.reshape(()), dtext, None, None, None
 
 
@@ -438,6 +440,7 @@ class _DecoderFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- model
+HEAD_MAX_BINS = 32   # include/ebc_hip.h EBC_HEAD_MAX_BINS
 resnet_backbones = ["resnet50", "resnet101", "resnet50x4", "resnet50x16", "resnet50x64"]
 vit_backbones = ["vit_b_16", "vit_b_32"]
 
@@ -462,6 +465,9 @@ class CLIP_EBC(nn.Module):
         if backbone not in vit_backbones + ["resnet50"]:
             raise NotImplementedError(f"backbone {backbone!r}: vit_b_16, vit_b_32 and resnet50 are on the MI355X path "
                                       "(SURVEY.md §8)")
+        if len(bins) > HEAD_MAX_BINS:
+            raise NotImplementedError(f"{len(bins)} bins: the HIP similarity head takes up to {HEAD_MAX_BINS} bins "
+                                      "(EBC_HEAD_MAX_BINS; the reference's largest bin table has 20)")
         self.backbone = backbone
         if backbone == "resnet50":
             from .synthetic import RN50_CHANNELS, RN50_EMBED

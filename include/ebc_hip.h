@@ -257,7 +257,10 @@ int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* 
                       float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream);
 /* Blockwise image-text similarity head (models/clip/model.py:200-217):
  * Z [P=B*HW, embed] projected features (NHWC rows) -> logits [B,NB,HW], exp [B,1,HW]; text [NB, embed];
- * embed = the CLIP joint width: 512 (ViT-B/16) or 1024 (ResNet-50), NB <= 16.
+ * embed = the CLIP joint width: 512 (ViT-B/16, ViT-B/32) or 1024 (ResNet-50), 1 <= NB <= EBC_HEAD_MAX_BINS (32: the
+ * reference's largest bin table has 20).  Up to 16 bins run the 16-slot kernel instances, 17 .. 32 bins the 32-slot ones
+ * (per-pixel register arrays of 32; normalised text rows in up to 64 KiB / 128 KiB of LDS at embed 512 / 1024, the
+ * backward 16 KiB + 16 B more); NB outside 1 .. 32 or another embed is EBC_E_UNSUPPORTED before any device work.
  * Backward: dZ (element type dtype_dz), d projection bias (column sums), d logit_scale; gscale (device scalar) scales the
  * upstream gradients (NULL = 1).  d bias / d logit_scale are summed deterministically (per-block partials in `workspace`,
  * ebc_head_bwd_workspace_bytes(P, embed) bytes, reduced in block order); workspace may be NULL when both are NULL.
@@ -266,6 +269,7 @@ int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* 
  * EBC_E_ARG, before any device work: P <= 0, HW <= 0 or P % HW != 0 (P is B whole images); NULL Z / text / logit_scale /
  * anchors / logits / expo (forward) or Z / text / logit_scale / anchors / dlogits / dexp / dZ (backward); dbias or dscale
  * given with a workspace that is NULL or too small.  ebc_cast_f32: NULL in / out, n % 4 != 0. */
+#define EBC_HEAD_MAX_BINS 32
 int ebc_head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
                  float* logits, float* expo, int P, int HW, int NB, int embed, ebc_stream_t stream);
 size_t ebc_head_bwd_workspace_bytes(int P, int embed);
@@ -288,6 +292,20 @@ size_t ebc_head_bwd_text_workspace_bytes(int P, int NB, int embed);
 int ebc_head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
                       const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
                       int embed, void* workspace, size_t workspace_bytes, ebc_stream_t stream);
+/* ebc_head_bwd_text for up to EBC_HEAD_MAX_BINS bins: the same operands, the same dtext and the same contract (raw-row
+ * gradient through the head's own F.normalize, g_k / 1e-12 on a clamped row, per-workgroup partials in plain stores
+ * summed in a fixed order, no float atomics, ebc_head_bwd's outputs untouched, the same EBC_E_ARG cases), with
+ * 1 <= NB <= 32 at embed 512 / 1024; EBC_E_UNSUPPORTED and a workspace size of 0 outside that.  ebc_head_bwd_text keeps
+ * its 16-bin bound and its arithmetic; this entry point passes the normalised text rows through LDS in groups of
+ * 16384 / embed rows, so its sums are formed in another order (equal within rounding, not bit-equal, at NB <= 16).
+ * Workspace: ceil(P / 64) workgroup partials of (NB * embed + 32) floats each -- [NB][embed] sums of dl[p][k] zn_p,
+ * then 32 slots of sum_p dl[p][k] logits[p][k] (slots k >= NB are zero):
+ *   ebc_head_bwd_text_wide_workspace_bytes(P, NB, embed) = ceil(P / 64) * (NB * embed + 32) * 4.
+ * (ebc_head_bwd_text's: ceil(P / 64) * (NB * embed + 16) * 4.) */
+size_t ebc_head_bwd_text_wide_workspace_bytes(int P, int NB, int embed);
+int ebc_head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
+                           const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
+                           int embed, void* workspace, size_t workspace_bytes, ebc_stream_t stream);
 int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

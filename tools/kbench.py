@@ -4,7 +4,8 @@ usage: python tools/kbench.py gemm M N K EPI [--reps R] [--dtype f16|bf16]   (EP
        python tools/kbench.py multi gemm:M,N,K,EPI attn:B ... [--rounds R]   (several classes, interleaved rounds)
        python tools/kbench.py attn B [--reps R]                              (fwd + bwd at L = 229, 12 heads)
        python tools/kbench.py conv B [--reps R]                              (decoder 3x3 conv fwd + BN stats, 768 ch)
-       python tools/kbench.py head B [--reps R]                              (similarity head fwd + bwd, f32 Z)
+       python tools/kbench.py head B [HW CH NB] [--reps R]                   (similarity head fwd + bwd + text gradient, f32 Z;
+                                                                              default 784 pixels a crop, width 512, 5 bins)
 Prints the HIP-event average per launch.  Operands are random (DVFS: zero-filled data reads high).
 """
 import argparse
@@ -82,14 +83,15 @@ def run(what, args, a):
         f = 4.0 * B * H * Lq * Lq * 64
         print(f"attn B={B}: fwd {tf:.2f} us ({f / tf / 1e6:.0f} TF/s)  bwd {tb:.2f} us ({2 * f / tb / 1e6:.0f} TF/s)")
     elif what == "head":
-        (B,) = args                                  # crops of 224 at reduction 8: 784 pixels each, embed 512, 5 bins
-        HW, CH, NB = 784, 512, 5
+        B = args[0]                                  # crops of 224 at reduction 8: 784 pixels each, embed 512, 5 bins
+        HW, CH, NB = (args[1:] + [784, 512, 5][len(args) - 1:])[:3]
         P = B * HW
         f32, f16 = _lib.dtype_code(torch.float32), _lib.dtype_code(torch.float16)
         Z = torch.randn(P, CH, device="cuda")
         text = torch.randn(NB, CH, device="cuda")
         ls = torch.full((1,), 4.6, device="cuda")
-        anchors = torch.tensor([0.0, 1.0, 2.0, 3.0, 4.2], device="cuda")
+        anchors = (torch.tensor([0.0, 1.0, 2.0, 3.0, 4.2], device="cuda") if NB == 5
+                   else torch.arange(NB, device="cuda", dtype=torch.float32) * 1.05)
         logits = torch.empty(B, NB, HW, device="cuda")
         expo = torch.empty(B, 1, HW, device="cuda")
         dl, de = torch.randn_like(logits), torch.randn_like(expo)
@@ -100,7 +102,13 @@ def run(what, args, a):
         ws = torch.empty(L.ebc_head_bwd_workspace_bytes(P, CH), device="cuda", dtype=torch.uint8)
         tb = timeit(lambda: L.ebc_head_bwd(f32, f16, p(Z), p(text), p(ls), p(anchors), p(dl), p(de), None, p(dZ), p(dbias),
                                            p(dscale), P, HW, NB, CH, p(ws), ws.numel(), st), a.reps)
-        print(f"head B={B}: fwd {tf:.2f} us ({P * CH * 4 / tf / 1e3:.0f} GB/s)  bwd {tb:.2f} us ({P * CH * 6 / tb / 1e3:.0f} GB/s)")
+        wide = "_wide" if NB > 16 else ""                 # the text gradient: ebc_head_bwd_text up to 16 bins, _wide above
+        dtext = torch.empty(NB, CH, device="cuda")
+        wt = torch.empty(getattr(L, f"ebc_head_bwd_text{wide}_workspace_bytes")(P, NB, CH), device="cuda", dtype=torch.uint8)
+        tt = timeit(lambda: getattr(L, "ebc_head_bwd_text" + wide)(f32, p(Z), p(text), p(ls), p(anchors), p(dl), p(de), None,
+                                                                  p(dtext), P, HW, NB, CH, p(wt), wt.numel(), st), a.reps)
+        print(f"head B={B} HW={HW} CH={CH} NB={NB}: fwd {tf:.2f} us ({P * CH * 4 / tf / 1e3:.0f} GB/s)  bwd {tb:.2f} us "
+              f"({P * CH * 6 / tb / 1e3:.0f} GB/s)  text{wide} {tt:.2f} us")
     elif what == "conv":
         (B,) = args
         H = W = 28
