@@ -1357,3 +1357,17 @@ int attention_bwd(int dtype, const void* qkv, const void* dout, const void* out,
                                                  E::BYTES == 2 ? touch : nullptr));
 }
 }  // namespace ebc
+
+// The entry points validate on the host, before any device work, then go to the launchers above (which vit.hip calls
+// directly, with its touch lists).
+extern "C" int ebc_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream)
+{
+    if (!qkv || !out) return EBC_E_ARG;
+    return ebc::attention_fwd(dtype, qkv, out, lse, B, L, H, (hipStream_t)stream);
+}
+extern "C" int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
+                                 float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream)
+{
+    if (!qkv || !dout || !out || !lse || !dqkv) return EBC_E_ARG;
+    return ebc::attention_bwd(dtype, qkv, dout, out, lse, delta_ws, dqkv, B, L, H, (hipStream_t)stream);
+}

@@ -54,6 +54,18 @@ inline bool ensure_lds(int bytes, hipStream_t st)
     return true;
 }
 
+// Hands out a workspace in 256-byte aligned pieces.  A null base is a dry run: take() returns null and `off` ends at
+// the bytes the layout needs (the *_workspace_bytes answers).
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class P> P* take(size_t bytes) {
+        P* p = base ? reinterpret_cast<P*>(base + off) : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
 // Wave-wide reductions on DPP (VALU lane moves) instead of __shfl_xor, which hipcc lowers to six
 // ds_bpermute LDS round trips each followed by lgkmcnt(0): quad xor-1 / xor-2, row half-mirror and
 // row mirror leave every lane with its 16-lane row's total, row_bcast:15 / row_bcast:31 fold the

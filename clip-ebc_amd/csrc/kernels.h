@@ -1,4 +1,5 @@
-// Internal launchers shared by the C-ABI entry points and the ViT orchestrator.
+// Internal launchers that more than one source file calls: the ViT and text-tower orchestrators (vit.hip, text.hip) and
+// the C-ABI entry points beside each launcher.  The similarity head (head.hip) has entry points only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -101,32 +102,11 @@ int embed_tokens(const float* patch, const float* cls, const float* pos, const f
 int layernorm_fwd_vpt(int dtype, float* X, const float* vpt, long vpt_bstride, int L, int NVPT, const float* gamma,
                       const float* beta, void* out, float* mean, float* rstd, int M, int D, hipStream_t st);
 // ln_1 backward that routes the prompt rows' gradient to vpt_rows [B][NVPT][D] (and zeroes them in dx_out /
-// dx_out_t): replaces layernorm_bwd + vpt_grad; vpt_sum then reduces the per-crop rows over the batch for
-// every layer in one launch
+// dx_out_t); vpt_sum then reduces the per-crop rows over the batch for every layer in one launch
 int layernorm_bwd_vpt(int dtype, const void* dy, const float* x, const float* mean, const float* rstd,
                       const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, int D, float* vpt_rows,
                       int L, int NVPT, hipStream_t st);
 int vpt_sum(const float* rows, float* const* dst, int layers, int B, int NVPT, int D, hipStream_t st);
-int vpt_grad(int dtype, float* dX, void* dXt, float* dvpt, int B, int L, int NVPT, int D, int per_batch, int accumulate,
-             hipStream_t st);
-int head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
-             float* logits, float* expo, int P, int HW, int NB, int embed, hipStream_t st);
-// d bias / d logit_scale as per-block partials (ws: head_bwd_ws_bytes) summed in block order by a second launch
-size_t head_bwd_ws_bytes(int P, int embed);
-int head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const float* logit_scale, const float* anchors,
-             const float* dlogits, const float* dexp, const float* gscale, void* dZ, float* dbias, float* dscale,
-             int P, int HW, int NB, int embed, void* ws, size_t wsb, hipStream_t st);
-// d (logits, exp) / d text [NB][embed] (the raw rows, through the head's F.normalize): per-block partials in ws
-// (head_bwd_text_ws_bytes), summed in block order by a second launch
-size_t head_bwd_text_ws_bytes(int P, int NB, int embed);
-int head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
-                  const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
-                  int embed, void* ws, size_t wsb, hipStream_t st);
-// the same for up to 32 bins: the text rows pass through LDS in groups (partials carry 32 dot slots)
-size_t head_bwd_text_wide_ws_bytes(int P, int NB, int embed);
-int head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
-                       const float* dlogits, const float* dexp, const float* gscale, float* dtext, int P, int HW, int NB,
-                       int embed, void* ws, size_t wsb, hipStream_t st);
 int cast_f32(int dtype, const float* in, void* out, size_t n, hipStream_t st);
 int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, hipStream_t st,
                   const TouchList* touch = nullptr);

@@ -560,17 +560,6 @@ namespace {
 constexpr int TW = 512, THEADS = 8, TMLP = 2048, TQKV = 3 * TW;
 constexpr size_t WGRAD_CNT_BYTES = 16 * 1024;
 
-inline size_t t_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct TCarver {
-    char* base; size_t off = 0;
-    template <class P> P* take(size_t bytes) {
-        P* p = base ? reinterpret_cast<P*>(base + off) : nullptr;
-        off += t_align(bytes);
-        return p;
-    }
-};
-
 struct TLayerW { void *qkv, *qkv_t, *out, *out_t, *fc, *fc_t, *proj, *proj_t; };
 struct TLayerSave {
     float *X1, *m1, *r1, *m2, *r2, *lse;
@@ -604,7 +593,7 @@ size_t wgrad_ws_max(int dtype, int Mp, int embed)
 TLayout text_carve(void* ws, int NB, int Lt, int layers, int embed, int dtype, int training)
 {
     const size_t M = (size_t)NB * Lt, es = dtype == EBC_F32 ? 4 : 2;
-    TCarver c{(char*)ws};
+    Carver c{(char*)ws};
     TLayout lay{};
     lay.Mp = (int)((M + 63) / 64 * 64);
     const int nsave = training ? layers : 1;

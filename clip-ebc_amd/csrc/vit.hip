@@ -1,5 +1,5 @@
 // Host-side orchestration of the CLIP ViT-B/16 and ViT-B/32 + deep-VPT encoder (forward, and dX-only backward
-// with the per-layer VPT gradients), plus the C-ABI wrappers of the individual kernels.
+// with the per-layer VPT gradients).  The single kernels' entry points are beside their kernels.
 //
 // Reference: CLIP_EBC._forward_vpt   models/clip/model.py:142-189
 //            ResidualAttentionBlock  models/clip/_clip/blocks.py:22-42
@@ -23,18 +23,6 @@
 namespace {
 
 constexpr int WIDTH = 768, HEADS = 12, MLP = 3072, QKVW = 3 * WIDTH;
-
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carver {
-    char* base; size_t off = 0; bool dry;
-    Carver(void* b, bool d) : base((char*)b), dry(d) {}
-    template <class P> P* take(size_t bytes) {
-        P* p = dry ? nullptr : reinterpret_cast<P*>(base + off);
-        off += align_up(bytes);
-        return p;
-    }
-};
 
 struct LayerSave {
     float *X1, *m1, *r1, *m2, *r2, *lse;
@@ -62,7 +50,7 @@ Layout carve(void* ws, int B, int L, int G, int KP, int layers, int dtype, int t
 {
     const size_t M = (size_t)B * L;
     const size_t es = dtype == EBC_F32 ? 4 : 2;
-    Carver c(ws, ws == nullptr);
+    ebc::Carver c{(char*)ws};
     Layout lay;
     const int nsave = training ? layers : 1;
     lay.X.resize(layers + 1);
@@ -376,102 +364,4 @@ extern "C" int ebc_vit_backward(const EbcVitWeights* w, int B, int H, int W, int
     // dvpt_l = sum over crops of the prompt rows, every layer in one launch (shared prompts)
     if (NV > 0 && dvpt && !per_batch) EBC_TRY(ebc::vpt_sum(lay.vpt_rows, dvpt, layers, B, NV, WIDTH, st));
     return EBC_OK;
-}
-
-// ---------------------------------------------------------------------------- kernel C-ABI
-// The single-kernel entry points validate on the host, before any device work (EBC_E_ARG); the in-library callers above
-// go to the ebc:: launchers directly.
-static bool ln_map_ok(int rpg, int gstride, int goff)
-{
-    return rpg <= 0 || (goff >= 0 && (long)goff + rpg <= (long)gstride);
-}
-extern "C" int ebc_layernorm_fwd(int dtype, const float* x, int rows_per_group, int group_stride, int group_offset,
-                                 const float* gamma, const float* beta, void* out, float* out_f32, float* mean,
-                                 float* rstd, int M, int D, ebc_stream_t stream)
-{
-    if (!x || !gamma || !beta || (!out && !out_f32) || (mean && !rstd)) return EBC_E_ARG;
-    if (!ln_map_ok(rows_per_group, group_stride, group_offset)) return EBC_E_ARG;
-    return ebc::layernorm_fwd(dtype, x, rows_per_group, group_stride, group_offset, gamma, beta, out, out_f32, mean,
-                              rstd, M, D, (hipStream_t)stream);
-}
-extern "C" int ebc_layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int rows_per_group,
-                                 int group_stride, int group_offset, const float* mean, const float* rstd,
-                                 const float* gamma, const float* dx_in, float* dx_out, void* dx_out_t, int M, int D,
-                                 ebc_stream_t stream)
-{
-    if (!dy || !x || !mean || !rstd || !gamma || !dx_out) return EBC_E_ARG;
-    if (!ln_map_ok(rows_per_group, group_stride, group_offset)) return EBC_E_ARG;
-    return ebc::layernorm_bwd(dtype, dy_f32, dy, x, rows_per_group, group_stride, group_offset, mean, rstd, gamma,
-                              dx_in, dx_out, dx_out_t, M, D, (hipStream_t)stream);
-}
-extern "C" int ebc_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream)
-{
-    if (!qkv || !out) return EBC_E_ARG;
-    return ebc::attention_fwd(dtype, qkv, out, lse, B, L, H, (hipStream_t)stream);
-}
-extern "C" int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
-                                 float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream)
-{
-    if (!qkv || !dout || !out || !lse || !dqkv) return EBC_E_ARG;
-    return ebc::attention_bwd(dtype, qkv, dout, out, lse, delta_ws, dqkv, B, L, H, (hipStream_t)stream);
-}
-extern "C" int ebc_head_fwd(int dtype_z, const void* Z, const float* text, const float* logit_scale, const float* anchors,
-                            float* logits, float* expo, int P, int HW, int NB, int embed, ebc_stream_t stream)
-{
-    if (!Z || !text || !logit_scale || !anchors || !logits || !expo) return EBC_E_ARG;
-    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
-    return ebc::head_fwd(dtype_z, Z, text, logit_scale, anchors, logits, expo, P, HW, NB, embed, (hipStream_t)stream);
-}
-extern "C" size_t ebc_head_bwd_workspace_bytes(int P, int embed)
-{
-    return ebc::head_bwd_ws_bytes(P, embed);
-}
-extern "C" int ebc_head_bwd(int dtype_z, int dtype_dz, const void* Z, const float* text, const float* logit_scale,
-                            const float* anchors, const float* dlogits, const float* dexp, const float* gscale, void* dZ,
-                            float* dbias, float* dscale, int P, int HW, int NB, int embed, void* workspace,
-                            size_t workspace_bytes, ebc_stream_t stream)
-{
-    if (!Z || !text || !logit_scale || !anchors || !dlogits || !dexp || !dZ) return EBC_E_ARG;
-    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
-    return ebc::head_bwd(dtype_z, dtype_dz, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dZ, dbias, dscale, P, HW,
-                         NB, embed, workspace, workspace_bytes, (hipStream_t)stream);
-}
-extern "C" size_t ebc_head_bwd_text_workspace_bytes(int P, int NB, int embed)
-{
-    if (NB > 16 || (embed != 512 && embed != 1024)) return 0;
-    return ebc::head_bwd_text_ws_bytes(P, NB, embed);
-}
-extern "C" int ebc_head_bwd_text(int dtype_z, const void* Z, const float* text, const float* logit_scale,
-                                 const float* anchors, const float* dlogits, const float* dexp, const float* gscale,
-                                 float* dtext, int P, int HW, int NB, int embed, void* workspace, size_t workspace_bytes,
-                                 ebc_stream_t stream)
-{
-    if (!Z || !text || !logit_scale || !anchors || !dlogits || !dexp || !dtext) return EBC_E_ARG;
-    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
-    return ebc::head_bwd_text(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, embed,
-                              workspace, workspace_bytes, (hipStream_t)stream);
-}
-extern "C" size_t ebc_head_bwd_text_wide_workspace_bytes(int P, int NB, int embed)
-{
-    return ebc::head_bwd_text_wide_ws_bytes(P, NB, embed);
-}
-extern "C" int ebc_head_bwd_text_wide(int dtype_z, const void* Z, const float* text, const float* logit_scale,
-                                      const float* anchors, const float* dlogits, const float* dexp, const float* gscale,
-                                      float* dtext, int P, int HW, int NB, int embed, void* workspace,
-                                      size_t workspace_bytes, ebc_stream_t stream)
-{
-    if (!Z || !text || !logit_scale || !anchors || !dlogits || !dexp || !dtext) return EBC_E_ARG;
-    if (P <= 0 || HW <= 0 || P % HW) return EBC_E_ARG;
-    return ebc::head_bwd_text_wide(dtype_z, Z, text, logit_scale, anchors, dlogits, dexp, gscale, dtext, P, HW, NB, embed,
-                                   workspace, workspace_bytes, (hipStream_t)stream);
-}
-extern "C" int ebc_im2col(int dtype, const float* x, void* out, int B, int H, int W, int patch, ebc_stream_t stream)
-{
-    if (!x || !out || B <= 0 || patch <= 0 || H < patch || W < patch) return EBC_E_ARG;
-    return ebc::im2col(dtype, x, out, B, H, W, patch, (hipStream_t)stream);
-}
-extern "C" int ebc_cast_f32(int dtype, const float* in, void* out, size_t n, ebc_stream_t stream)
-{
-    if (!in || !out) return EBC_E_ARG;
-    return ebc::cast_f32(dtype, in, out, n, (hipStream_t)stream);
 }

@@ -255,7 +255,7 @@ int ebc_layernorm_bwd(int dtype, int dy_f32, const void* dy, const float* x, int
 int ebc_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int L, int H, ebc_stream_t stream);
 int ebc_attention_bwd(int dtype, const void* qkv, const void* dout, const void* out, const float* lse,
                       float* delta_ws, void* dqkv, int B, int L, int H, ebc_stream_t stream);
-/* Blockwise image-text similarity head (models/clip/model.py:200-217):
+/* Blockwise image-text similarity head (head.hip; models/clip/model.py:200-217):
  * Z [P=B*HW, embed] projected features (NHWC rows) -> logits [B,NB,HW], exp [B,1,HW]; text [NB, embed];
  * embed = the CLIP joint width: 512 (ViT-B/16, ViT-B/32) or 1024 (ResNet-50), 1 <= NB <= EBC_HEAD_MAX_BINS (32: the
  * reference's largest bin table has 20).  Up to 16 bins run the 16-slot kernel instances, 17 .. 32 bins the 32-slot ones

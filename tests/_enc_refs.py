@@ -1,5 +1,5 @@
 """Plain float64 restatements of the operations behind the encoder-side kernels: LayerNorm with the row map
-(vit_misc.hip), multi-head attention (attention.hip) and the blockwise similarity head (vit_misc.hip), and the input
+(vit_misc.hip), multi-head attention (attention.hip) and the blockwise similarity head (head.hip), and the input
 generators of tests/test_gpu_encoder_kernels.py.
 
 Written from the operations' definitions (nn.LayerNorm, nn.MultiheadAttention's scaled-dot-product core, F.normalize /

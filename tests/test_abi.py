@@ -142,6 +142,97 @@ EBC_E_UNSUPPORTED = -3
 BF16 = 2
 STORE, GELU, RESID, GELU_BWD = 0, 1, 2, 3
 
+# The single-kernel entry points' answers to calls they refuse on the host: every NULL in turn, P % HW, the bin and
+# width ranges, a short workspace, a dtype that is none of the three, a row map that leaves its group, and pairs of
+# faults that pin the order of the tests (a NULL operand is EBC_E_ARG before a bin count out of range is
+# EBC_E_UNSUPPORTED).  The codes are part of the ABI: callers tell a bad call from a shape the library does not run.
+# Every pointer is bogus, so a call that launched would not return.
+_A, _U, _BIG = EBC_E_ARG, EBC_E_UNSUPPORTED, 1 << 30
+_CALLS = {   # entry point -> (argument names in order, a call that is accepted)
+    "ebc_head_fwd": ("dtype Z text ls anchors logits expo P HW NB embed stream",
+                     dict(dtype=F32, Z=_X, text=_X, ls=_X, anchors=_X, logits=_X, expo=_X, P=8, HW=4, NB=5, embed=512)),
+    "ebc_head_bwd": ("dtype dtype_dz Z text ls anchors dl de gscale dZ dbias dscale P HW NB embed ws wsb stream",
+                     dict(dtype=F32, dtype_dz=F32, Z=_X, text=_X, ls=_X, anchors=_X, dl=_X, de=_X, dZ=_X, P=8, HW=4, NB=5,
+                          embed=512, wsb=0)),
+    "ebc_head_bwd_text": ("dtype Z text ls anchors dl de gscale dtext P HW NB embed ws wsb stream",
+                          dict(dtype=F32, Z=_X, text=_X, ls=_X, anchors=_X, dl=_X, de=_X, dtext=_X, P=8, HW=4, NB=5,
+                               embed=512, ws=_X, wsb=_BIG)),
+    "ebc_layernorm_fwd": ("dtype x rpg gs go gamma beta out outf mean rstd M D stream",
+                          dict(dtype=F16, x=_X, rpg=0, gs=0, go=0, gamma=_X, beta=_X, out=_X, mean=_X, rstd=_X, M=8, D=768)),
+    "ebc_layernorm_bwd": ("dtype dy_f32 dy x rpg gs go mean rstd gamma dx_in dx_out dxt M D stream",
+                          dict(dtype=F16, dy_f32=0, dy=_X, x=_X, rpg=0, gs=0, go=0, mean=_X, rstd=_X, gamma=_X, dx_out=_X,
+                               M=8, D=768)),
+    "ebc_attention_fwd": ("dtype qkv out lse B L H stream", dict(dtype=F16, qkv=_X, out=_X, lse=_X, B=1, L=5, H=2)),
+    "ebc_attention_bwd": ("dtype qkv dout out lse delta dqkv B L H stream",
+                          dict(dtype=F16, qkv=_X, dout=_X, out=_X, lse=_X, delta=_X, dqkv=_X, B=1, L=5, H=2)),
+    "ebc_im2col": ("dtype x out B H W patch stream", dict(dtype=F16, x=_X, out=_X, B=2, H=32, W=32, patch=16)),
+    "ebc_cast_f32": ("dtype src out n stream", dict(dtype=F16, src=_X, out=_X, n=8)),
+}
+_CALLS["ebc_head_bwd_text_wide"] = _CALLS["ebc_head_bwd_text"]
+_HEAD_NULLS = [(dict([(k, None)]), _A) for k in ("Z", "text", "ls", "anchors", "dl", "de")]
+_HEAD_SHAPE = [(dict(P=8, HW=3), _A), (dict(P=0), _A), (dict(NB=0), _U), (dict(NB=33), _U), (dict(embed=768), _U),
+               (dict(dtype=3), _A), (dict(NB=40, Z=None), _A), (dict(NB=33, HW=3), _A), (dict(NB=33, dtype=3), _U),
+               (dict(embed=768, dtype=3), _U)]
+_TEXT = _HEAD_NULLS + [(dict(dtext=None), _A)] + _HEAD_SHAPE + [
+    (dict(ws=None), _A), (dict(wsb=0), _A), (dict(dtype=3, ws=None), _A), (dict(embed=768, ws=None), _U),
+    (dict(NB=0, wsb=0), _U)]
+_REJECTED = {
+    "ebc_head_fwd": _HEAD_NULLS[:4] + [(dict(logits=None), _A), (dict(expo=None), _A)] + _HEAD_SHAPE,
+    "ebc_head_bwd": _HEAD_NULLS + [(dict(dZ=None), _A)] + _HEAD_SHAPE + [
+        (dict(dtype_dz=3), _A), (dict(dbias=_X), _A), (dict(dscale=_X), _A),
+        (dict(dbias=_X, ws=_X, wsb=(512 + 1) * 4 - 1), _A), (dict(dbias=_X, P=64, HW=64, ws=_X, wsb=(512 + 1) * 4), _A),
+        (dict(dbias=_X, NB=33), _U), (dict(dscale=_X, embed=768, ws=_X, wsb=8), _U), (dict(dbias=_X, dtype=3), _A)],
+    # the narrow text gradient stops at 16 bins; its workspace holds ceil(P / 64) * (NB * embed + 16) floats
+    "ebc_head_bwd_text": _TEXT + [(dict(NB=17), _U), (dict(NB=17, dtype=3), _U), (dict(NB=17, text=None), _A),
+                                  (dict(wsb=(5 * 512 + 16) * 4 - 1), _A)],
+    "ebc_head_bwd_text_wide": _TEXT + [(dict(wsb=(5 * 512 + 32) * 4 - 1), _A), (dict(wsb=(5 * 512 + 16) * 4), _A)],
+    "ebc_layernorm_fwd": [(dict(x=None), _A), (dict(gamma=None), _A), (dict(beta=None), _A), (dict(out=None), _A),
+                          (dict(rstd=None), _A), (dict(rpg=4, gs=7, go=4), _A), (dict(rpg=4, gs=7, go=-1), _A),
+                          (dict(D=700), _U), (dict(D=1024), _U), (dict(M=0), _U), (dict(dtype=3), _A),
+                          (dict(dtype=3, D=512), _A), (dict(x=None, D=700), _A), (dict(rpg=4, gs=7, go=4, M=0), _A),
+                          (dict(D=700, dtype=3), _U)],
+    "ebc_layernorm_bwd": [(dict([(k, None)]), _A) for k in ("dy", "x", "mean", "rstd", "gamma", "dx_out")] + [
+        (dict(rpg=4, gs=7, go=4), _A), (dict(D=700), _U), (dict(M=0), _U), (dict(dtype=3), _A), (dict(dtype=3, D=512), _A),
+        (dict(gamma=None, M=0), _A), (dict(rpg=49, gs=82, go=34, D=700), _A), (dict(M=-1, dtype=3), _U)],
+    "ebc_attention_fwd": [(dict(qkv=None), _A), (dict(out=None), _A), (dict(L=0), _U), (dict(L=20000), _U), (dict(B=0), _U),
+                          (dict(H=0), _U), (dict(dtype=3), _A), (dict(dtype=3, L=300), _A), (dict(qkv=None, L=0), _A),
+                          (dict(L=0, dtype=3), _U)],
+    "ebc_attention_bwd": [(dict([(k, None)]), _A) for k in ("qkv", "dout", "out", "lse", "dqkv")] + [
+        (dict(L=0), _U), (dict(L=20000), _U), (dict(B=0), _U), (dict(dtype=F32, delta=None), _A),
+        (dict(L=300, delta=None), _A), (dict(dtype=3), _A), (dict(lse=None, B=0), _A), (dict(L=20000, delta=None), _U),
+        (dict(dtype=3, L=300, delta=None), _A)],
+    "ebc_im2col": [(dict(x=None), _A), (dict(out=None), _A), (dict(B=0), _A), (dict(patch=0), _A), (dict(H=8), _A),
+                   (dict(H=40), _A), (dict(H=36, W=36, patch=6), _A), (dict(H=64, W=64, patch=64), _A), (dict(dtype=3), _A),
+                   (dict(x=None, H=40), _A)],
+    "ebc_cast_f32": [(dict(src=None), _A), (dict(out=None), _A), (dict(n=6), _A), (dict(dtype=3), _A), (dict(n=6, dtype=3), _A)],
+}
+
+
+@pytest.mark.parametrize("fn,kw,rc", [(fn, kw, rc) for fn, cases in _REJECTED.items() for kw, rc in cases],
+                         ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else str(v))
+def test_moved_entry_points_keep_their_return_codes(lib, fn, kw, rc):
+    names, valid = _CALLS[fn]
+    args = {**valid, **kw}
+    assert getattr(lib, fn)(*[args.get(n) for n in names.split()]) == rc
+
+
+@pytest.mark.parametrize("fn,args,nbytes", [
+    ("ebc_head_bwd_workspace_bytes", (0, 512), 0), ("ebc_head_bwd_workspace_bytes", (-5, 512), 0),
+    ("ebc_head_bwd_workspace_bytes", (8, 512), 513 * 4), ("ebc_head_bwd_workspace_bytes", (3136, 1024), 98 * 1025 * 4),
+    ("ebc_head_bwd_workspace_bytes", (33, 768), 2 * 769 * 4),
+    ("ebc_head_bwd_text_workspace_bytes", (8, 5, 512), (5 * 512 + 16) * 4),
+    ("ebc_head_bwd_text_workspace_bytes", (3136, 16, 1024), 49 * (16 * 1024 + 16) * 4),
+    ("ebc_head_bwd_text_workspace_bytes", (8, 17, 512), 0), ("ebc_head_bwd_text_workspace_bytes", (8, 5, 768), 0),
+    ("ebc_head_bwd_text_workspace_bytes", (0, 5, 512), 0), ("ebc_head_bwd_text_workspace_bytes", (8, 0, 512), 0),
+    ("ebc_head_bwd_text_workspace_bytes", (8, 5, 0), 0),
+    ("ebc_head_bwd_text_wide_workspace_bytes", (8, 17, 512), (17 * 512 + 32) * 4),
+    ("ebc_head_bwd_text_wide_workspace_bytes", (6272, 20, 1024), 98 * (20 * 1024 + 32) * 4),
+    ("ebc_head_bwd_text_wide_workspace_bytes", (65, 32, 1024), 2 * (32 * 1024 + 32) * 4),
+    ("ebc_head_bwd_text_wide_workspace_bytes", (8, 33, 512), 0), ("ebc_head_bwd_text_wide_workspace_bytes", (8, 5, 768), 0),
+    ("ebc_head_bwd_text_wide_workspace_bytes", (0, 5, 512), 0), ("ebc_head_bwd_text_wide_workspace_bytes", (8, 0, 512), 0)])
+def test_head_workspace_sizes(lib, fn, args, nbytes):
+    assert getattr(lib, fn)(*args) == nbytes
+
 
 def _gemm(lib, dtype=F16, epi=STORE, out_f32=0, A=_X, B=_X, C=_X, bias=None, resid=None, aux=None, M=16, N=64, K=64):
     return lib.ebc_gemm(dtype, epi, out_f32, A, B, C, bias, resid, aux, M, N, K, None)

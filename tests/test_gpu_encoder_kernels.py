@@ -1,5 +1,5 @@
-"""The LayerNorm, attention and similarity-head entry points (vit_misc.hip, attention.hip), one kernel at a time,
-per element against the float64 references of tests/_enc_refs.py (pinned to torch in tests/test_enc_refs_cpu.py).
+"""The LayerNorm, attention and similarity-head entry points (vit_misc.hip, attention.hip, head.hip), one kernel at a
+time, per element against the float64 references of tests/_enc_refs.py (pinned to torch in tests/test_enc_refs_cpu.py).
 
 Every output buffer carries sentinel guard rows / elements that must survive, every workspace is sized exactly from its
 *_workspace_bytes call plus guard bytes, and every check prints "RATIO <name> <largest error / bound>" before it asserts.

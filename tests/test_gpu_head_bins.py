@@ -1,4 +1,4 @@
-"""The similarity head at 17 .. 32 bins (vit_misc.hip: the 32-slot instances of head_fwd_kernel / head_bwd_kernel, and
+"""The similarity head at 17 .. 32 bins (head.hip: the 32-slot instances of head_fwd_kernel / head_bwd_kernel, and
 head_text_wide_bwd_kernel behind ebc_head_bwd_text_wide), per element against float64.
 
 No new tolerance: the forward and backward cases ARE tests/test_gpu_encoder_kernels.py's test_head_fwd / test_head_bwd,

@@ -1,4 +1,4 @@
-"""ebc_head_bwd_text (vit_misc.hip head_text_bwd_kernel + head_text_finalize_kernel): the similarity head's gradient
+"""ebc_head_bwd_text (head.hip head_text_bwd_kernel + head_text_finalize_kernel): the similarity head's gradient
 with respect to the raw text rows, per element against a float64 restatement written here on top of tests/_enc_refs.py.
 
 Conventions of tests/test_gpu_encoder_kernels.py: guarded outputs, the workspace sized exactly plus guard bytes, every
@@ -15,7 +15,7 @@ from ebc_amd import _lib
 
 pytestmark = pytest.mark.gpu
 F64, U, TRANS, DT, WS_GUARD = E.F64, E.U, E.TRANS, E.DT, E.WS_GUARD
-PPB = 64                                  # pixels a workgroup (vit_misc.hip HEAD_TXT_PPB), 16 a wave
+PPB = 64                                  # pixels a workgroup (head.hip HEAD_TXT_PPB), 16 a wave
 
 hold = _Hold()
 

@@ -21,8 +21,6 @@ int probe_start(int, int, int, int, int, int, int, int, hipStream_t) { return -1
 void probe_stop(int, hipStream_t) {}
 }  // namespace ebc
 
-constexpr size_t GEMM_CNT_BYTES = 16 * 1024;     // gemm.hip's split-K counter block
-
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 __global__ void fill_f16(_Float16* p, size_t n, unsigned seed, float scale)
